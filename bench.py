@@ -1,7 +1,11 @@
 """Headline benchmark: 256x256 hand images/s for one full G+D step (optimize_parameters).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times K steps, optionally writes what the last timed step computed (--dump-outputs) and
+prints the line.  --full adds everything else the line can carry: the side regions (other precisions, norms, sizes, the
+graph step, gradient parity, RCCL with one rank, inference), the N-GPU side regions and the CPU-oracle baseline.
 
 Started without a launcher (no WORLD_SIZE in the environment) and with --gpus N > 1, bench.py starts
 its own N ranks as CHILD processes - one per GPU, RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set, before
@@ -17,6 +21,7 @@ RCCL.  Prints ONE JSON line on rank 0.
 import argparse
 import json
 import os
+import random
 import sys
 import time
 
@@ -249,9 +254,11 @@ def infer_main(a):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(a.steps):
-        gen(g_in)
+        y = gen(g_in)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, image=y)
     ips = B * a.steps / dt
     print(json.dumps({
         "metric": "256x256 hand images/sec (Generator inference)", "value": round(ips, 2),
@@ -664,7 +671,7 @@ def rccl_child_run(steps, warmup, batch, size, timeout_s=600):
                MASTER_PORT=str(_free_port()))
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup),
-           "--batch", str(batch), "--size", str(size), "--no-cpu-baseline", "--dp-side-runs"]
+           "--batch", str(batch), "--size", str(size), "--full", "--no-cpu-baseline", "--dp-side-runs"]
     try:
         out = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout_s, env=env)
     except subprocess.TimeoutExpired:
@@ -769,6 +776,43 @@ def selftest_ranks():
     dist.destroy_process_group()
 
 
+DUMP_MAX_IMAGE = 8 << 20        # --dump-outputs: elements of an output image kept whole (32 MB); beyond, a seeded sample
+DUMP_WEIGHTS = 1 << 20          # --dump-outputs: weight values kept per network (4 MB), at seeded positions
+
+
+def _seeded_sample(t, n, seed):
+    """`t` as float32 on the host: whole if it has at most `n` elements, else `n` of them, flattened, at positions drawn
+    from a CPU generator seeded with `seed` (sorted; the same positions for the same size on every run)"""
+    t = t.detach()
+    if t.numel() > n:
+        idx = torch.randint(0, t.numel(), (n,), generator=torch.Generator().manual_seed(seed)).sort().values
+        t = t.reshape(-1)[idx.to(t.device)]
+    return t.float().contiguous().cpu().numpy()
+
+
+def dump_outputs(out_dir, model=None, image=None):
+    """--dump-outputs DIR: what the last timed step handed its caller, one DIR/<name>.npy each (at most ~45 MB in all).
+    Training (model): the six losses of get_current_errors() (float64 scalars, loss_<name>.npy), the generated image
+    fake_p2 (NCHW float32) and, per network, the weights the step's Adam updates left, in the reference's logical layout
+    (state_dict order, floating-point entries) at DUMP_WEIGHTS seeded positions.  Inference: the Generator's output (image)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {}
+    if model is not None:
+        for k, v in model.get_current_errors().items():
+            arrays["loss_" + k] = np.asarray(float(v), dtype=np.float64)
+        image = model.fake_p2
+        for i, name in enumerate(("netG", "netD_PB", "netD_PP")):
+            sd = getattr(model, name).state_dict()
+            flat = torch.cat([v.detach().reshape(-1).float() for v in sd.values() if v.is_floating_point()])
+            arrays[name + "_weights_sample"] = _seeded_sample(flat, DUMP_WEIGHTS, 1000 + i)
+            del flat
+    if image is not None:
+        arrays["fake_p2" if model is not None else "generator_output"] = _seeded_sample(image, DUMP_MAX_IMAGE, 999)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
+
+
 def main():
     _json_only_stdout()
     ap = argparse.ArgumentParser()
@@ -778,7 +822,15 @@ def main():
     ap.add_argument("--batch", type=int, default=32, help="per-GPU batch")
     ap.add_argument("--size", type=int, default=256)
     ap.add_argument("--norm", default="instance", choices=["instance", "batch"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline figure: the side regions (16-bit mode, --norm batch, "
+                         "graph step, direct and hybrid kernels, gradient parity, RCCL world 1, inference, 512x512), the "
+                         "N-GPU side regions and the CPU-oracle baseline (off by default: a plain run times only the "
+                         "headline steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed to DIR/<name>.npy: losses, the "
+                         "generated image and a seeded sample of the updated weights (inference: the Generator output)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU-oracle baseline")
     ap.add_argument("--no-winograd", action="store_true",
                     help="direct implicit-GEMM kernels for every conv (default: fp32 runs the 3x3 stride-1 convs "
                          "with >= 128x128 channels on Winograd F(6x6,3x3); 16-bit mode runs them direct on "
@@ -792,22 +844,22 @@ def main():
     ap.add_argument("--cpu-threads", type=int, default=CPU_THREADS, help=argparse.SUPPRESS)
     ap.add_argument("--cpu-max-steps", type=int, default=10, help=argparse.SUPPRESS)
     ap.add_argument("--cpu-all-cores", type=float, default=0.0, metavar="SECONDS",
-                    help="also time the CPU oracle with os.cpu_count() threads inside this budget (off by default)")
+                    help="with --full: also time the CPU oracle with os.cpu_count() threads inside this budget (off by default)")
     ap.add_argument("--selftest-ranks", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--launch-timeout", type=float, default=2400.0,
                     help="seconds after which a self-started multi-rank run (a hung collective) is ended with exit code 124")
     ap.add_argument("--dp-side-runs", action="store_true",
-                    help="with MMH_FORCE_DP=1 and one rank: also run the data-parallel side regions of an N-GPU launch")
+                    help="with --full, MMH_FORCE_DP=1 and one rank: also run the data-parallel side regions of an N-GPU launch")
     ap.add_argument("--dp-regions", default="all",
-                    help="N-GPU launch: comma-separated side regions to run (dp_bf16_path, dp_norm_batch, dp_norm_batch_o1, "
+                    help="N-GPU launch with --full: comma-separated side regions to run (dp_bf16_path, dp_norm_batch, dp_norm_batch_o1, "
                          "dp_bf16_path_nopersist, dp_size512_bf16_b4, dp_size512_bf16_b4_norm_batch); default all")
     ap.add_argument("--dp-512", action="store_true",
-                    help="N-GPU launch: also time configs[4]'s shape (512x512, per-GPU batch 4, bf16); default only at N = 4")
+                    help="N-GPU launch with --full: also time configs[4]'s shape (512x512, per-GPU batch 4, bf16); default only at N = 4")
     ap.add_argument("--share-gpu-gloo", action="store_true",
                     help="TEST AID (tests/test_dp_gpu.py): all N ranks on GPU 0 over the gloo backend - exercises every line of "
                          "the N-GPU bench on a one-GPU box; the throughput it prints means nothing")
     ap.add_argument("--no-side-runs", action="store_true",
-                    help="skip the extra driver-visible measurements (direct-kernel steps, set_input in the loop, "
+                    help="with --full: skip the extra driver-visible measurements (direct-kernel steps, set_input in the loop, "
                          "16-bit mode, --norm batch, RCCL world-1, inference, 512x512); profiling runs use this to "
                          "keep the kernel trace to the headline path")
     ap.add_argument("--mode", default="train", choices=["train", "infer"],
@@ -846,6 +898,9 @@ def main():
                             checkpoints_dir="/tmp/mmh_bench", distributed=world > 1 or force_dp,
                             opt_level="O1" if a.dtype == "bf16" else "O0")
     peak = PEAK_BF16_MFMA_TF if a.dtype == "bf16" else PEAK_F32_MFMA_TF
+    # the image pools draw from Python's global `random` (util/image_pool.py): seeded, so that the same arguments give the
+    # same discriminator inputs on every run (--dump-outputs compares builds output for output)
+    random.seed(49 + rank)
     model = MMHandModel(opt)
     H = W = a.size
     batch = synthetic_batch_gpu(a.batch, H, W, 49 + rank, dev)
@@ -893,6 +948,8 @@ def main():
         dt, dt_fastest = float(t[0]), float(-t[1])
     losses = {k: float(v) for k, v in model.get_current_errors().items()}
     peak_gib = round(torch.cuda.max_memory_allocated(dev) / 2 ** 30, 2)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, model=model)     # before any side region touches the model
 
     def timed_steps(n, before_step=None):
         """n more optimize_parameters() calls bracketed like the main region; ms per step (max over ranks)."""
@@ -912,8 +969,9 @@ def main():
 
     n_rccl = rccl_ranks(dev)
     side = {}
-    side_ok = not a.no_side_runs and world == 1 and not force_dp
-    dp_side = (world > 1 and not a.no_side_runs) or (force_dp and a.dp_side_runs)
+    side_ok = a.full and not a.no_side_runs and world == 1 and not force_dp
+    dp_side = a.full and ((world > 1 and not a.no_side_runs) or (force_dp and a.dp_side_runs))
+    cpu_base = a.full and not a.no_cpu_baseline
     dp_info = {}
     cpu_child = None
     if getattr(model, "dp", False):
@@ -921,7 +979,7 @@ def main():
                    if getattr(model, "dp_native", None) else f"dist.all_reduce ({getattr(model, 'dp_native_why', '-')})",
                    "inplace_param_grads": bool(getattr(model, "dp_accum", False)),
                    "ms_per_step_fastest_rank": round(dt_fastest / a.steps * 1e3, 2)}
-    if world > 1 and rank == 0 and not a.no_cpu_baseline:
+    if world > 1 and rank == 0 and cpu_base:
         # N-GPU launch: the CPU oracle runs on rank 0's host cores WHILE the side regions below run on the GPUs (16 of the
         # host's threads; every rank's own host work is one thread), collected before the line is printed
         cpu_child = cpu_baseline_start(H, W, a.norm)
@@ -1146,7 +1204,7 @@ def main():
         line.update(side)
         if cpu_child is not None:
             line["cpu_baseline"] = cpu_baseline_collect(cpu_child)
-        if world == 1 and not force_dp and not a.no_cpu_baseline:
+        if world == 1 and not force_dp and cpu_base:
             line["cpu_baseline"] = cpu_baseline_with_sweep(H, W, a.norm)
             # SURVEY.md §8(d) asks for os.cpu_count() threads.  On the GPU box's 256 logical CPUs oneDNN is far slower
             # at 128+ threads than at 16 (tools/cpu_probe.py; one B=2 step did not finish in 240 s): opt-in

@@ -213,3 +213,45 @@ def test_bench_norm_batch_o1_side_run_reports_host_enqueue(dev):
     out2 = bench.side_train_run(dev, 2, 64, 1, warmup=1, opt_level="O1", lib_options={"lp16_persist": (0, 1)})
     assert out2["losses_finite"]
     L.call("mmh_set_option", b"lp16_persist", 1)
+
+
+def test_bench_plain_run_times_the_headline_only_and_dumps_what_it_computed(dev, tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR` without --full: one line with the headline figures of K
+    timed steps and none of the side regions or the CPU baseline; DIR holds what the last timed step computed (the six
+    losses, the generated image, seeded samples of the updated weights), and a second run with the same arguments computes
+    the same, bit for bit (seeded inputs, weights and image-pool draws: batch 16 over 5 steps overflows the 50-image pools)."""
+    import json
+    import os
+    import subprocess
+    import sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    runs = []
+    for i in range(2):
+        d = tmp_path / f"run{i}"
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--batch", "16", "--size", "64",
+                              "--steps", "4", "--warmup", "1", "--dump-outputs", str(d)],
+                             capture_output=True, text=True, timeout=900)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, out.stdout[-1000:]
+        j = json.loads(lines[0])
+        assert j["steps"] == 4 and j["warmup"] == 1 and j["n_gpus"] == 1 and j["dtype"] == "f32"
+        assert j["unit"] == "images/s" and j["higher_is_better"] is True and j["ms_per_step"] > 0
+        assert abs(j["value"] * j["ms_per_step"] / 1e3 / 16 - 1) < 1e-3, j       # images/s = batch / the timed step
+        for k in ("cpu_baseline", "set_input_in_loop", "direct_path", "bf16_path", "graph_step", "gradient_parity",
+                  "hybrid_path", "norm_batch", "dp_rccl_world1", "size512_bf16_b4", "infer_b64_f32"):
+            assert k not in j, k
+        files = {f.name[:-len(".npy")]: np.load(f) for f in d.iterdir()}
+        assert sum(f.stat().st_size for f in d.iterdir()) <= 64 << 20
+        for k, v in j["losses"].items():
+            assert files["loss_" + k].dtype == np.float64 and abs(float(files["loss_" + k]) - v) <= 1e-5 + 1e-6 * abs(v), k
+        assert files["fake_p2"].shape == (16, 3, 64, 64) and files["fake_p2"].dtype == np.float32
+        assert np.isfinite(files["fake_p2"]).all() and np.abs(files["fake_p2"]).max() <= 1.0       # tanh head
+        for n in ("netG", "netD_PB", "netD_PP"):
+            w = files[n + "_weights_sample"]
+            assert w.dtype == np.float32 and w.shape == (1 << 20,) and np.isfinite(w).all() and w.std() > 0, n
+        assert len(files) == len(j["losses"]) + 4, sorted(files)
+        runs.append(files)
+    for k, v in runs[0].items():
+        assert np.array_equal(v, runs[1][k]), k

@@ -278,7 +278,7 @@ def test_bench_two_ranks_on_one_gpu_carry_every_multi_gpu_key(dev):
     import json
     import subprocess
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--share-gpu-gloo", "--batch", "2",
-                          "--size", "64", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--dp-512"],
+                          "--size", "64", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--dp-512"],
                          capture_output=True, text=True, timeout=1500)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -391,7 +391,7 @@ def test_bench_eight_ranks_on_one_gpu_carry_every_multi_gpu_key(dev):
     # (eight processes time-slice the one GPU - 4 minutes for all six regions - so this line runs the two regions of
     # BASELINE.json configs[2] and of SyncBN; the two-rank test above runs every region)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--share-gpu-gloo", "--batch", "2",
-                          "--size", "64", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
+                          "--size", "64", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline",
                           "--dp-regions", "dp_bf16_path,dp_norm_batch"],
                          capture_output=True, text=True, timeout=2400)
     assert out.returncode == 0, out.stderr[-2000:]

@@ -316,6 +316,42 @@ def test_bench_refuses_a_mismatched_launch():
     assert out.returncode != 0 and "1-rank launch" in out.stderr
 
 
+def test_bench_dump_outputs_writes_float_arrays_at_seeded_positions(monkeypatch, tmp_path):
+    """bench.dump_outputs (--dump-outputs DIR) on host tensors: the losses as float64 scalars, the image whole while it is
+    small and as a seeded sample beyond DUMP_MAX_IMAGE, per network DUMP_WEIGHTS weights (logical state_dict order) at
+    positions that are the same on every call; and the CLI offers --dump-outputs and --full."""
+    from collections import OrderedDict
+    from types import SimpleNamespace
+    import bench
+    from mmhand_amd.networks import Discriminator, Generator
+    nets = dict(netG=Generator([3, 42, 6], 3, 8, "instance", True, 2).init_weights("normal", 1),
+                netD_PB=Discriminator(24, 8, "batch", True, 2).init_weights("normal", 2),
+                netD_PP=Discriminator(6, 8, "instance", True, 2).init_weights("normal", 3))
+    img = torch.randn(2, 3, 16, 16, generator=torch.Generator().manual_seed(0))
+    model = SimpleNamespace(fake_p2=img, get_current_errors=lambda: OrderedDict([("pair_L1loss", torch.tensor(0.25)),
+                                                                                   ("D_PP", 1.5)]), **nets)
+    monkeypatch.setattr(bench, "DUMP_WEIGHTS", 500)
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), model=model)
+    got = {f.name: np.load(f) for f in (tmp_path / "a").iterdir()}
+    assert sorted(got) == sorted(["loss_pair_L1loss.npy", "loss_D_PP.npy", "fake_p2.npy", "netG_weights_sample.npy",
+                                  "netD_PB_weights_sample.npy", "netD_PP_weights_sample.npy"])
+    assert got["loss_pair_L1loss.npy"].dtype == np.float64 and float(got["loss_D_PP.npy"]) == 1.5
+    assert np.array_equal(got["fake_p2.npy"], img.numpy())
+    for n, net in nets.items():
+        w = got[n + "_weights_sample.npy"]
+        flat = torch.cat([v.reshape(-1).float() for v in net.state_dict().values() if v.is_floating_point()]).numpy()
+        assert w.dtype == np.float32 and w.shape == (500,) and np.isin(w, flat).all(), n
+        assert np.array_equal(w, np.load(tmp_path / "b" / (n + "_weights_sample.npy"))), n
+    monkeypatch.setattr(bench, "DUMP_MAX_IMAGE", 100)
+    bench.dump_outputs(str(tmp_path / "c"), image=img)
+    s = np.load(tmp_path / "c" / "generator_output.npy")
+    assert s.shape == (100,) and s.dtype == np.float32 and np.isin(s, img.numpy()).all()
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True,
+                         timeout=300)
+    assert out.returncode == 0 and "--dump-outputs" in out.stdout + out.stderr and "--full" in out.stdout + out.stderr
+
+
 def test_cpu_baseline_thread_sweep_reports_the_fastest(monkeypatch):
     """bench.cpu_baseline_with_sweep (VERDICT r4 #5b): 16 / 32 / 64 threads, the fastest is `value`, all three are kept."""
     import bench

@@ -21,5 +21,5 @@ python3 - "$O/cpu_all_cores_line.log" > $P/r04_cpu_all_cores.json <<'PY'
 import json, sys
 l = [x for x in open(sys.argv[1]) if x.startswith("{")][-1]
 j = json.loads(l)
-print(json.dumps({"command": "python bench.py --steps 2 --warmup 1 --no-side-runs --cpu-all-cores 200", "cpu_baseline": j.get("cpu_baseline")}, indent=1))
+print(json.dumps({"command": "python bench.py --full --steps 2 --warmup 1 --no-side-runs --cpu-all-cores 200", "cpu_baseline": j.get("cpu_baseline")}, indent=1))
 PY

@@ -3,8 +3,8 @@
 # side configurations, PMC passes for the 16-bit kernels.  Outputs under gpurun_out/r02final/.
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r02final; mkdir -p $O
 cd $R
-python bench.py --steps 20 --warmup 5 > $O/bench_f32_full.log 2>&1
-python bench.py --dtype bf16 --steps 20 --warmup 5 > $O/bench_bf16_full.log 2>&1
+python bench.py --full --steps 20 --warmup 5 > $O/bench_f32_full.log 2>&1
+python bench.py --full --dtype bf16 --steps 20 --warmup 5 > $O/bench_bf16_full.log 2>&1
 python bench.py --norm batch --steps 10 --warmup 3 --no-cpu-baseline --no-side-runs > $O/bench_f32_bn.log 2>&1
 python bench.py --norm batch --dtype bf16 --steps 10 --warmup 3 --no-cpu-baseline --no-side-runs > $O/bench_bf16_bn.log 2>&1
 python bench.py --mode infer > $O/infer_f32.log 2>&1

@@ -4,8 +4,8 @@
 # Outputs under gpurun_out/r03final/ (copied into profiles/r03_* by hand: see profiles/README.md).
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r03final; mkdir -p $O
 cd $R
-python bench.py --steps 20 --warmup 5 > $O/bench_f32_full.log 2>&1
-python bench.py --dtype bf16 --steps 20 --warmup 5 --no-side-runs > $O/bench_bf16_full.log 2>&1
+python bench.py --full --steps 20 --warmup 5 > $O/bench_f32_full.log 2>&1
+python bench.py --full --dtype bf16 --steps 20 --warmup 5 --no-side-runs > $O/bench_bf16_full.log 2>&1
 python tools/step_breakdown.py --dtype bf16 > $O/breakdown_bf16.txt 2>&1
 python tools/step_breakdown.py --dtype f32 > $O/breakdown_f32.txt 2>&1
 python tools/bench_lp16h.py > $O/bench_lp16h.txt 2>&1

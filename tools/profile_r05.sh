@@ -24,8 +24,8 @@ python tools/roofline_from_trace.py $O/prof_bf16 "conv_lp16h2_kernel<false, 1, f
 for f in prof_infer prof_512 prof_f32 prof_bf16; do find $O/$f -name "*kernel_stats.csv" -exec cp {} $O/$f.kernel_stats.csv \; ; rm -rf $O/$f; done
 # part C: the driver's own command (every side key on one line), and the same with the 16-bit step as the headline region
 cd $R
-python bench.py > $O/full_f32_line.log 2>&1
-python bench.py --dtype bf16 --no-side-runs > $O/full_bf16_line.log 2>&1
+python bench.py --full > $O/full_f32_line.log 2>&1
+python bench.py --full --dtype bf16 --no-side-runs > $O/full_bf16_line.log 2>&1
 # MFMA-busy of the two forms of the halo kernel (A/B build: two waves per SIMD, one wave per SIMD) and of the new stride-2 dgrad
 bash $R/tools/pmc_r05.sh > $O/pmc_lp16.txt 2>&1
 ls -la $O

@@ -52,8 +52,8 @@ for f in prof_infer prof_512 prof_f32 prof_bf16; do
 done
 need $O/roofline_f32_trace.txt 200 roofline_f32; need $O/roofline_bf16_trace.txt 200 roofline_bf16
 # ---- D
-python bench.py > $O/full_f32_line.log 2>&1 || fail=1
-python bench.py --dtype bf16 --no-side-runs > $O/full_bf16_line.log 2>&1 || fail=1
+python bench.py --full > $O/full_f32_line.log 2>&1 || fail=1
+python bench.py --full --dtype bf16 --no-side-runs > $O/full_bf16_line.log 2>&1 || fail=1
 grep -q '^{' $O/full_f32_line.log || { echo "profile_r06.sh: stage [full line] printed no JSON line" >&2; fail=1; }
 ls -la $O
 [ $fail -eq 0 ] && echo "profile_r06.sh: ok" || { echo "profile_r06.sh: INCOMPLETE (see above)" >&2; exit 1; }
