@@ -827,6 +827,30 @@ int mmh_rccl_bind(const char* librccl_path);
 int mmh_rccl_comm_ranks(void* comm);
 int mmh_allreduce_bucket(void* comm, void* buf, int64_t count, int dtype, mmh_stream_t s);
 
+/* ---- image quality metrics (pytorch_ssim/__init__.py:17-37, baselines/quantitative_on_benchmarks/utils.py:100-111) ----
+ * replaces ssim(pred, gt) of the Evaluator, one image at a time, plus mean |a-b| and mean (a-b)^2 from the same pass.
+ * Every image pair is [C][H][W] and mapped to [0, 1] on load: v = stored * scale + offset (generator output in [-1, 1]:
+ * 0.5 / 0.5; 8-bit pixels: 1/255 / 0).  taps (host memory, `window` floats, window odd, 3 .. 15): the 1-D window as
+ * pytorch_ssim.gaussian(window, 1.5) returns it (fp32, normalised by torch's fp32 sum - its last bit is torch's summation
+ * order, which is why the caller passes it); the 2-D window is their fp32 outer product; zero padding of window / 2;
+ * ssim_map = ((2 mu_a mu_b + c1)(2 s_ab + c2)) / ((mu_a^2 + mu_b^2 + c1)(s_a^2 + s_b^2 + c2)) (c1 = 0.01^2, c2 = 0.03^2
+ * in the reference).  out[b][0] = mean of ssim_map over C, H, W (the reference's size_average=False), out[b][1] =
+ * mean |a-b|, out[b][2] = mean (a-b)^2, float64.  Within 1e-6 of the same formula in float64 (fp32 moments, each
+ * taken about a pixel inside its own window); no atomics: an image's result is bit-identical run to run and does not
+ * depend on the other images of the batch; ssim(a, b) == ssim(b, a) bit for bit and ssim(x, x) == 1.
+ * ws: mmh_image_metrics_ws_bytes(B, C, H, W, window) bytes (0 = the arguments are refused).                             */
+enum { MMH_U8 = 3 };             /* mmh_image_src only: uint8 pixels                                                    */
+typedef struct mmh_image_src {
+    const void* ptr;                 /* element (b, c, h, w) at ptr + b sb + c sc + h sh + w sw (elements)              */
+    int32_t dtype;                   /* MMH_F32 | MMH_BF16 | MMH_FP16 | MMH_U8                                          */
+    float scale, offset;             /* [0, 1] value = stored * scale + offset                                          */
+    int64_t sb, sc, sh, sw;          /* element strides; negative allowed (BGR pixels read as RGB: sc = -1)             */
+} mmh_image_src;
+size_t mmh_image_metrics_ws_bytes(int B, int C, int H, int W, int window);
+int mmh_image_metrics(const mmh_image_src* a, const mmh_image_src* b, int B, int C, int H, int W, int window, const float* taps,
+                      double c1, double c2, void* ws, size_t ws_bytes, double* out /* [B][3]: ssim, l1, mse */,
+                      mmh_stream_t s);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }

@@ -1,0 +1,172 @@
+"""Scores generated hand images on a held-out split: per-image SSIM (the reference Evaluator's metric, utils.py:100-111),
+L1 and PSNR, all on images mapped to [0, 1] (generator output (x + 1) / 2, PNG pixels u8 / 255; see mmhand_amd/metrics.py).
+
+Generator mode - runs a checkpoint over the generation split of a prepared directory (the pairs aug.py generates) and
+scores each output against its target image H2:
+
+    python -m mmhand_amd.evaluate --name CKP [--checkpoints_dir checkpoints] [--which_epoch latest] --dataroot DIR
+        --dataset rhd|stb [--augmentation_ratio R] [--batchSize 16] [--bf16] [--gpu 0] [--window 11]
+        [--results_json PATH] [--per_image_csv PATH]
+
+Directory mode - scores the PNGs aug.py wrote (<DIR>/<folder of the target>/<name>) against the target colour PNGs:
+
+    python -m mmhand_amd.evaluate --generated DIR --dataroot DIR --dataset rhd|stb [--augmentation_ratio R] ...
+
+Both print one summary line (SSIM_avg, SSIM_std, L1_avg, PSNR_avg, n) and write it with the options used as JSON."""
+import argparse
+import csv
+import json
+import os
+import re
+import sys
+
+import numpy as np
+import torch
+
+from .metrics import QualityMeter
+
+DOMAIN = ("Both images are mapped to [0, 1] before scoring: generator output (x + 1) / 2, PNG pixels u8 / 255 - the range "
+          "a written PNG represents, so scoring the generator's tensors and scoring aug.py's PNGs agree up to quantisation.")
+
+
+def build_parser():
+    p = argparse.ArgumentParser(prog="python -m mmhand_amd.evaluate", description=__doc__.split("\n\n")[0] + "  " + DOMAIN,
+                                formatter_class=argparse.RawDescriptionHelpFormatter)
+    src = p.add_mutually_exclusive_group(required=True)
+    src.add_argument("--name", help="checkpoint name: <checkpoints_dir>/<name>/<which_epoch>_net_netG.pth")
+    src.add_argument("--generated", help="directory of aug.py's output PNGs, scored instead of running a generator")
+    p.add_argument("--checkpoints_dir", default="checkpoints")
+    p.add_argument("--which_epoch", default="latest")
+    p.add_argument("--dataroot", required=True, help="prepared RHD / STB directory (annotation.pickle + PNGs)")
+    p.add_argument("--dataset", required=True, choices=("rhd", "stb"))
+    p.add_argument("--augmentation_ratio", type=float, default=None,
+                   help="the generation split is the first (1 - ratio) share; a root with 'test' in its path serves all")
+    p.add_argument("--batchSize", type=int, default=16)
+    p.add_argument("--bf16", action="store_true", help="the generator's 16-bit (bf16 MFMA) inference mode")
+    p.add_argument("--gpu", type=int, default=0)
+    p.add_argument("--window", type=int, default=11, help="SSIM window, odd, 3 .. 15 (the reference's default 11)")
+    p.add_argument("--results_json", default=None,
+                   help="default: <checkpoints_dir>/<name>/eval_<which_epoch>_<dataset>.json, or <generated>/eval_<dataset>.json")
+    p.add_argument("--per_image_csv", default=None, help="one row per target: target, source, ssim, l1, psnr")
+    return p
+
+
+def strip_module(sd):
+    """Evaluator._get_weights (utils.py:126-136): DataParallel / DDP checkpoints carry a leading 'module.'"""
+    return type(sd)((k[len("module."):] if k.startswith("module.") else k, v) for k, v in sd.items())
+
+
+def infer_generator_config(sd):
+    """(ngf, n_blocks, norm, use_dropout) of a Generator state_dict (values may be tensors or shapes): ngf from the first
+    stem conv, n_blocks from the model.att.<i> indices, batch norm iff running statistics are stored, dropout iff the
+    second conv of conv_block_stream1 sits at index 6 (5 without the Dropout layer; InferenceGenerator's fold reads it)."""
+    sd = strip_module(sd)
+    w = sd.get("model.stream1_down.1.weight")
+    if w is None:
+        raise ValueError("not a Generator state_dict: no model.stream1_down.1.weight")
+    ngf = int((w.shape if hasattr(w, "shape") else w)[0])
+    blocks = {int(m.group(1)) for k in sd for m in [re.match(r"model\.att\.(\d+)\.", k)] if m}
+    n_blocks = max(blocks) + 1 if blocks else 0
+    norm = "batch" if any(k.endswith("running_mean") for k in sd) else "instance"
+
+    def conv_at(i):         # a 4-D weight (conv) at index i; under batch norm the norm after the conv at 5 sits at 6
+        v = sd.get(f"model.att.0.conv_block_stream1.{i}.weight")
+        return v is not None and len(v.shape if hasattr(v, "shape") else v) == 4
+
+    use_dropout = conv_at(6)
+    if n_blocks and not use_dropout and not conv_at(5):
+        raise ValueError("not a Generator state_dict: no second conv in model.att.0.conv_block_stream1")
+    return ngf, n_blocks, norm, use_dropout
+
+
+def _opt(args):
+    from .options import default_train_opt
+    opt = default_train_opt(batchSize=args.batchSize, local_rank=args.gpu, isTrain=False)
+    opt.dataroot, opt.dataset, opt.augmentation_ratio, opt.distributed = (args.dataroot, args.dataset,
+                                                                          args.augmentation_ratio, False)
+    return opt
+
+
+def _score_generator(args, ckpt, dev):
+    from .data import HandFolderLoader
+    from .inference import InferenceGenerator
+    from .networks import Generator
+    sd = strip_module(torch.load(ckpt, map_location="cpu"))
+    ngf, n_blocks, norm, use_dropout = infer_generator_config(sd)
+    net = Generator(input_nc=[3, 42, 6], output_nc=3, ngf=ngf, norm_layer=norm, use_dropout=use_dropout, n_blocks=n_blocks)
+    net.load_state_dict(sd)
+    gen = InferenceGenerator(net.to(dev).eval(), use_graph=True, bf16=args.bf16)
+    loader = HandFolderLoader(_opt(args), device=dev, decoded=True)
+    meter = QualityMeter("pm1", args.window)
+    for s in loader:
+        fake = gen([s["H1"], torch.cat((s["P1"], s["P2"]), 1), torch.cat((s["D1"], s["D2"]), 1)])
+        # gen returns its graph's static output buffer: the metric is enqueued here, before the next replay
+        meter.feed(fake, s["H2"], [{"target": t, "source": h} for t, h in zip(s["H2_path"], s["H1_path"])])
+    return meter, {"ngf": ngf, "n_blocks": n_blocks, "norm": norm, "use_dropout": use_dropout}
+
+
+def _read_generated(path):
+    from .data import _read_bgr
+    if os.path.isfile(path):
+        return _read_bgr(path)
+    npy = os.path.splitext(path)[0] + ".npy"            # aug.py's fallback without PIL: RGB uint8 arrays
+    if os.path.isfile(npy):
+        return np.ascontiguousarray(np.load(npy)[:, :, ::-1])
+    raise SystemExit(f"--generated: {path} is missing (aug.py writes <DIR>/<folder of the target>/<name>)")
+
+
+def _score_directory(args, dev):
+    from .data import HandFolderLoader, _read_bgr
+    loader = HandFolderLoader(_opt(args), device=dev)
+    meter = QualityMeter("u8_bgr_hwc", args.window)
+    idx = loader.indices()
+    for i in range(0, len(idx), args.batchSize):
+        tgts = [loader.image_target[j] for j in idx[i:i + args.batchSize]]
+        srcs = [loader.image_source[j] for j in idx[i:i + args.batchSize]]
+        gen = [_read_generated(os.path.join(args.generated, *t.split("/")[-2:])) for t in tgts]
+        ref = [_read_bgr(t) for t in tgts]
+        for g, r, t in zip(gen, ref, tgts):
+            if g.shape != r.shape:
+                raise SystemExit(f"--generated: {t}: generated image {g.shape} vs target {r.shape}")
+        meter.feed(torch.from_numpy(np.stack(gen)).to(dev), torch.from_numpy(np.stack(ref)).to(dev),
+                   [{"target": t, "source": s} for t, s in zip(tgts, srcs)])
+    return meter, {}
+
+
+def main(argv=None):
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    if not (3 <= args.window <= 15 and args.window % 2 == 1):
+        parser.error(f"--window {args.window}: the SSIM window is odd, from 3 to 15")
+    if args.batchSize < 1:
+        parser.error("--batchSize must be >= 1")
+    ckpt = None
+    if args.name:
+        ckpt = os.path.join(args.checkpoints_dir, args.name, f"{args.which_epoch}_net_netG.pth")
+        if not os.path.isfile(ckpt):
+            raise SystemExit(f"evaluate: no checkpoint {ckpt} (--name / --checkpoints_dir / --which_epoch)")
+    elif not os.path.isdir(args.generated):
+        raise SystemExit(f"evaluate: --generated {args.generated} is not a directory")
+    torch.cuda.set_device(args.gpu)
+    dev = torch.device("cuda", args.gpu)
+    meter, config = _score_generator(args, ckpt, dev) if ckpt else _score_directory(args, dev)
+    res = meter.result()
+    summary = res["summary"]
+    print(json.dumps(summary))
+    out = args.results_json or (os.path.join(args.checkpoints_dir, args.name, f"eval_{args.which_epoch}_{args.dataset}.json")
+                                if ckpt else os.path.join(args.generated, f"eval_{args.dataset}.json"))
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, "w") as fh:
+        json.dump({"summary": summary, "options": vars(args), "generator": config or None,
+                   "domain": "[0, 1]: generator output (x + 1) / 2, PNG pixels u8 / 255"}, fh, indent=1)
+    if args.per_image_csv:
+        with open(args.per_image_csv, "w", newline="") as fh:
+            w = csv.writer(fh)
+            w.writerow(["target", "source", "ssim", "l1", "psnr"])
+            for r in res["rows"]:
+                w.writerow([r["target"], r["source"], repr(r["ssim"]), repr(r["l1"]), repr(r["psnr"])])
+    return res
+
+
+if __name__ == "__main__":
+    main(sys.argv[1:])

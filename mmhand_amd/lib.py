@@ -15,6 +15,7 @@ LIB_PATH = os.environ.get("MMH_LIB_PATH") or os.path.join(_HERE, "libmmhand_hip.
 PAD_ZERO, PAD_REFLECT = 0, 1
 ACT_NONE, ACT_RELU, ACT_TANH = 0, 1, 2
 F32, BF16, FP16 = 0, 1, 2
+U8 = 3          # mmh_image_src only
 
 
 class ConvDesc(C.Structure):
@@ -27,6 +28,12 @@ class ConvDesc(C.Structure):
 class PlaneSrc(C.Structure):
     """mirror of mmh_plane_src"""
     _fields_ = [("ptr", C.c_void_p), ("C", C.c_int32),
+                ("sb", C.c_int64), ("sc", C.c_int64), ("sh", C.c_int64), ("sw", C.c_int64)]
+
+
+class ImageSrc(C.Structure):
+    """mirror of mmh_image_src"""
+    _fields_ = [("ptr", C.c_void_p), ("dtype", C.c_int32), ("scale", C.c_float), ("offset", C.c_float),
                 ("sb", C.c_int64), ("sc", C.c_int64), ("sh", C.c_int64), ("sw", C.c_int64)]
 
 
@@ -183,6 +190,8 @@ SIGNATURES = {
     "mmh_rccl_bind": (_i, [C.c_char_p]),
     "mmh_rccl_comm_ranks": (_i, [_vp]),
     "mmh_allreduce_bucket": (_i, [_vp, _vp, _i64, _i, _vp]),
+    "mmh_image_metrics_ws_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "mmh_image_metrics": (_i, [C.POINTER(ImageSrc), C.POINTER(ImageSrc), _i, _i, _i, _i, _i, _vp, _d, _d, _vp, _sz, _vp, _vp]),
 }
 
 _lib = None
