@@ -384,7 +384,11 @@ class MMHandModel(torch.nn.Module):
             # the dropout salt, the image pools' decisions - and that form also runs eagerly (warm-up, fallback), so the
             # replayed step is the eager one bit for bit.
             self.graph_step = bool(getattr(opt, "graph_step", False) or os.environ.get("MMH_GRAPH_STEP") == "1")
-            if self.graph_step and getattr(opt, "distributed", False) and dist.is_initialized():
+            # MMH_FORCE_DP=1: take the data-parallel code path even with one rank (RCCL smoke test)
+            self.dp = self.world > 1 or (os.environ.get("MMH_FORCE_DP") == "1" and dist.is_initialized())
+            if self.graph_step and (self.dp or (getattr(opt, "distributed", False) and dist.is_initialized())):
+                # decided on self.dp, not on opt.distributed alone: MMH_FORCE_DP=1 takes the data-parallel step too, which
+                # never calls DevicePool.begin_iteration() and counts its Adam steps on the host
                 self.pprint("--graph_step: single-process only (the data-parallel step interleaves collectives); off")
                 self.graph_step = False
             Pool = (lambda n: DevicePool(n, opt.DG_ratio)) if self.graph_step else ImagePool
@@ -427,8 +431,6 @@ class MMHandModel(torch.nn.Module):
             self.optimizer_D_PP = FlatAdam(self.netD_PP, opt.lr, betas)
             self.optimizers = [self.optimizer_G, self.optimizer_D_PB, self.optimizer_D_PP]
             self.schedulers = [get_scheduler(o, opt) for o in self.optimizers]
-            # MMH_FORCE_DP=1: take the data-parallel code path even with one rank (RCCL smoke test)
-            self.dp = self.world > 1 or (os.environ.get("MMH_FORCE_DP") == "1" and dist.is_initialized())
             if self.dp:
                 self._init_data_parallel()
             self.skipped_steps = 0
@@ -458,6 +460,7 @@ class MMHandModel(torch.nn.Module):
                 self._graph_state = "warmup"
                 self._graph_warm = max(2, int(os.environ.get("MMH_GRAPH_WARMUP", "3")))
                 self._graph_iters = 0
+                self._graph_max_batch = 0       # the largest batch seen: the shape worth capturing
                 self.graph_replays = 0
                 self.graph_error = None
                 self._salt = torch.zeros(1, dtype=torch.int64, device=self.device)
@@ -856,6 +859,7 @@ class MMHandModel(torch.nn.Module):
         try:
             L.call("mmh_u64_add", ops._ptr(self._salt), 0x9E3779B97F4A7C15, ops._stream())
             self._step_body()
+            self._seed_after = ops._seed_counter[0]     # where an iteration leaves the host's seed counter (_replayed)
         finally:
             L.call("mmh_set_dropout_salt", None)
 
@@ -874,14 +878,21 @@ class MMHandModel(torch.nn.Module):
         self._graph_iters += 1
         if self._graph_state == "replay" and not getattr(self, "_graph_odd", False):
             self._graph.replay()
-            self.graph_replays += 1
+            self._replayed()
             self.__dict__.update(self._graph_outputs)      # (an odd-shaped batch in between had re-pointed them)
             return
-        if self._graph_state == "warmup" and self._graph_iters > self._graph_warm and os.environ.get("MMH_GRAPH_CAPTURE", "1") != "0":
+        if self._graph_state == "replay" and B > self._graph_batch and not getattr(self, "_graph_said_larger", False):
+            self._graph_said_larger = True
+            self.pprint("--graph_step: batches of %d run eagerly, the captured iteration holds %d" % (B, self._graph_batch))
+        # the captured iteration freezes its batch's shape: the short last batch of an epoch is not the one to capture (every
+        # full batch would then run eagerly for good) - the capture waits for a batch as large as the largest seen
+        self._graph_max_batch = max(self._graph_max_batch, B)
+        if (self._graph_state == "warmup" and self._graph_iters > self._graph_warm and B == self._graph_max_batch
+                and os.environ.get("MMH_GRAPH_CAPTURE", "1") != "0"):
             try:
                 self._capture_step(B)
                 self._graph.replay()        # capture executes nothing: this replay IS the iteration
-                self.graph_replays += 1
+                self._replayed()
                 return
             except Exception as e:          # noqa: BLE001 - any capture failure: stay eager, say why
                 self._graph, self._graph_state = None, "eager"
@@ -892,6 +903,17 @@ class MMHandModel(torch.nn.Module):
                     pool.begin_iteration(B, self.device, decide=False)     # the decisions already drawn for this iteration
                 ops.lp_grads_reset()
         self._graph_body()
+
+    def _replayed(self):
+        """the host's share of an iteration that ran as a replay - what FlatAdam.step and _graph_body do on the host in the
+        eager form and a replay, all device work, does not.  The Adam kernels rewrote the three flat buffers: the derived
+        copies the HOST knows (per-weight caches, the batches' `stale` flags) are those of the weights before this replay,
+        and an eager forward between replays (test(), a validation pass, a short batch) would read them.  Dictionary work
+        only, nothing is enqueued; the tensors the graph itself reads stay alive in _graph_keep."""
+        self.graph_replays += 1
+        for o in self.optimizers:
+            ops.bump_weights_epoch(within=o.net.flat_param)
+        ops.set_dropout_seed(self._seed_after)      # an eager forward draws the seeds it draws behind an eager iteration
 
     def _capture_step(self, B):
         torch.cuda.synchronize()
