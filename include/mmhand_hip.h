@@ -168,6 +168,15 @@ int mmh_wino_gemm(const void* V, const void* U, void* M, int64_t tiles, int K, i
  * this network by 3e-3, a backward one cannot (profiles/r03_wino_grad_split.txt: Winograd dgrad alone 6e-6).  */
 int mmh_wino_gemm_levels(const void* V, const void* U, void* M, int64_t tiles, int K, int N,
                          int nbatch, int levels, mmh_stream_t s);
+/* The 16 Winograd-domain GEMMs of F(2x2,3x3) (V [16][tiles][K], U [16][K][N] -> M [16][tiles][N], fp32) with the
+ * summation chosen per call.  levels = 2: a fresh MFMA chain per 32-deep k-step, folded into the totals by vector adds -
+ * the definition of the direct two-level fprop and of the 64-plane GEMMs - which mmh_wino_gemm_levels never runs for
+ * 16 planes (it folds 64 planes only and keeps doing so).  Fixed summation order, no atomics; a tile's result does not
+ * depend on the number of tiles.  Needs K % 32 == 0, N % 32 == 0, N >= 64.  Between mmh_wino_input(tile 2) and
+ * mmh_wino_output(tile 2) it is the forward of ops.set_winograd_mode("bwd_f2") for the 3x3 stride-1 convs of the
+ * reference's PATBlock conv stack (models/Generator.py:40-113).                                                       */
+int mmh_wino_gemm_levels16(const void* V, const void* U, void* M, int64_t tiles, int K, int N, int levels,
+                           mmh_stream_t s);
 /* The F(6x6,3x3) filter transform of MANY fp32 filters in one launch (after an optimizer step a network's 74
  * transforms are 8-25 us launches that cannot fill the chip).  table: n rows of six int64 in device memory -
  * {w pointer, U pointer, Cin, Cout, flip_transpose, first block} - entry e owning the 256-thread blocks

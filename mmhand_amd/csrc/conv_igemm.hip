@@ -3019,8 +3019,11 @@ static int launch_wino_gemm_t(const WinoGemmKP& p, hipStream_t st) {
     return mmh::check_launch("wino_gemm_kernel");
 }
 
+// fold16: the caller asked for the two-level sum whatever the plane count (mmh_wino_gemm_levels16: the 16 planes of the
+// F(2x2,3x3) forward).  wino_gemm_kernel<BN, 2> never reads the plane count but as the extent of its work list, so the
+// 16-plane form is the same instantiation on a shorter list; mmh_wino_gemm[_levels] keep folding 64 planes only.
 static int wino_gemm_v2(const float* V, const float* U, float* Mo, long long tiles, int K, int N, hipStream_t st,
-                        int nbatch, int levels) {
+                        int nbatch, int levels, bool fold16 = false) {
     WinoGemmKP p{};
     p.A = V; p.B = U; p.C = Mo;
     p.M = (int)tiles; p.K = K; p.N = N; p.P = nbatch;
@@ -3029,7 +3032,7 @@ static int wino_gemm_v2(const float* V, const float* U, float* Mo, long long til
     p.NT = (N + bn - 1) / bn;
     p.W = nbatch * p.MT * p.NT;
     p.Wx = (p.W + 7) / 8;
-    const bool two = (levels ? levels : g_wino_gemm_levels) == 2 && nbatch == 64 && K > WINO_FOLD * BK;   // nothing to fold below 2 blocks
+    const bool two = (levels ? levels : g_wino_gemm_levels) == 2 && (nbatch == 64 || fold16) && K > WINO_FOLD * BK;   // nothing to fold below 2 blocks
     p.nb = std::min(p.Wx, 32 * g_wino_gemm_occ);       // 32 CUs per XCD
     if (two) return bn == 128 ? launch_wino_gemm_t<128, 2>(p, st) : launch_wino_gemm_t<64, 2>(p, st);
     return bn == 128 ? launch_wino_gemm_t<128, 1>(p, st) : launch_wino_gemm_t<64, 1>(p, st);
@@ -3463,6 +3466,15 @@ int mmh_wino_gemm_levels(const void* V, const void* U, void* M, int64_t tiles, i
                 "mmh_wino_gemm_levels: bad arguments (fp32; levels 1 | 2)");
     return wino_gemm(static_cast<const float*>(V), static_cast<const float*>(U), static_cast<float*>(M), tiles, K, N,
                      mmh::as_stream(s), nbatch, levels);
+}
+
+int mmh_wino_gemm_levels16(const void* V, const void* U, void* M, int64_t tiles, int K, int N, int levels, mmh_stream_t s) {
+    MMH_REQUIRE(V && U && M && tiles > 0 && K > 0 && K % 32 == 0 && N >= 64 && N % 32 == 0 && (levels == 1 || levels == 2),
+                "mmh_wino_gemm_levels16: bad arguments (fp32, 16 planes; K %% 32 == 0, N %% 32 == 0, N >= 64; levels 1 | 2)");
+    MMH_REQUIRE(tiles * (long long)std::max(K, N) < (1ll << 30), "mmh_wino_gemm_levels16: tensor too large");
+    MMH_REQUIRE(g_wino_gemm_v2, "mmh_wino_gemm_levels16: needs the persistent kernel (option wino_gemm_v2)");
+    return wino_gemm_v2(static_cast<const float*>(V), static_cast<const float*>(U), static_cast<float*>(M), tiles, K, N,
+                        mmh::as_stream(s), 16, levels, true);
 }
 
 int mmh_wino_output(const void* M, void* y, const void* bias, int B, int H, int W, int C, int act, int tile,

@@ -63,6 +63,7 @@ SIGNATURES = {
     "mmh_wino_input_dy": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
     "mmh_wino_gemm": (_i, [_vp, _vp, _vp, _i64, _i, _i, _i, _i, _vp]),
     "mmh_wino_gemm_levels": (_i, [_vp, _vp, _vp, _i64, _i, _i, _i, _i, _vp]),
+    "mmh_wino_gemm_levels16": (_i, [_vp, _vp, _vp, _i64, _i, _i, _i, _vp]),
     "mmh_wino_weights_multi": (_i, [_vp, _i, _i64, _vp]),
     "mmh_prep_weights_lp16_multi": (_i, [_vp, _i, _i64, _vp]),
     "mmh_wino_output": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _vp]),

@@ -23,6 +23,7 @@ from . import lib as L
 from . import ops
 from .networks import Discriminator, Generator, VGGHead, discriminators_lockstep
 from .ops import pad4
+from .options import check_exact_fwd
 
 
 MERGE_D_PASSES = os.environ.get("MMH_MERGE_D", "1") != "0"
@@ -324,11 +325,13 @@ class MMHandModel(torch.nn.Module):
         self.overflow = False
         self.world = dist.get_world_size() if (getattr(opt, "distributed", False)
                                                and dist.is_initialized()) else 1
+        check_exact_fwd(opt)
         if getattr(opt, "fp32_exact_grads", False):
-            ops.set_winograd_mode("bwd")     # process-wide, like MMH_WINOGRAD=bwd (one model family per process)
-        elif os.environ.get("MMH_WINOGRAD") in ("bwd", "0"):
+            # process-wide, like MMH_WINOGRAD=bwd | bwd_f2 (one model family per process)
+            ops.set_winograd_mode("bwd_f2" if getattr(opt, "fp32_exact_fwd", "direct") == "wino2" else "bwd")
+        elif os.environ.get("MMH_WINOGRAD") in ("bwd", "bwd_f2", "0"):
             # the environment form of the same choice: the direct fprop's two-level summation comes with it
-            ops.set_winograd_mode("bwd" if os.environ["MMH_WINOGRAD"] == "bwd" else "off")
+            ops.set_winograd_mode("off" if os.environ["MMH_WINOGRAD"] == "0" else os.environ["MMH_WINOGRAD"])
         seed = getattr(opt, "seed", 49)
         # dropout masks: an independent stream per rank, as each reference rank has its own RNG
         # (the weights are seeded identically on every rank and broadcast from rank 0).  ImagePool

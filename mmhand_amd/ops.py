@@ -285,23 +285,32 @@ USE_WINOGRAD = os.environ.get("MMH_WINOGRAD", "1") != "0"
 # those of the direct path; dgrad and wgrad stay on F(6x6,3x3), whose rounding differences stay what they are (1e-5 on
 # the gradients, profiles/r03_wino_grad_split.txt) instead of being amplified into mask flips (3e-3).  The backward
 # computes the transformed input V itself (one extra input transform per conv) and runs the fused dy pass.
-WINOGRAD_FPROP = os.environ.get("MMH_WINOGRAD", "1") != "bwd"
+WINOGRAD_FPROP = os.environ.get("MMH_WINOGRAD", "1") not in ("bwd", "bwd_f2")
+# MMH_WINOGRAD=bwd_f2 (ops.set_winograd_mode("bwd_f2"), train option --fp32_exact_fwd wino2): the same hybrid with the forward
+# of the eligible 3x3 convs (_wino2_fwd_ok) on F(2x2,3x3) with two-level summation in its 16 GEMMs (mmh_wino_gemm_levels16).
+# The transform coefficients are 0, +-1, +-1/2: no rounding beyond a few additions, 2.25x fewer multiplications than the direct
+# kernel, the same summation definition.  Everything else - the other forward convs, dgrad, wgrad - runs as in "bwd".
+WINO2_FWD = os.environ.get("MMH_WINOGRAD", "1") == "bwd_f2"
+# smallest Cin*Cout the F(2x2,3x3) two-level forward takes: from the interleaved A/B against the direct two-level fprop
+# (tools/ab_wino2_fwd.py); MMH_WINO2_FWD_MIN overrides
+WINO2_FWD_MIN = int(os.environ.get("MMH_WINO2_FWD_MIN", str(256 * 256)))
 
 
 def set_winograd_mode(mode, direct_levels=None):
     """"all" (default: every pass of the eligible fp32 3x3 convs on Winograd), "bwd" (direct fprop, Winograd dgrad + wgrad:
-    the gradient-exact hybrid), "off" (direct kernels everywhere).
-    direct_levels (1 | 2; default 2 for "bwd" and "off", 1 for "all"; MMH_DIRECT_LEVELS overrides the default): summation
+    the gradient-exact hybrid), "bwd_f2" ("bwd" with the eligible forward convs on two-level F(2x2,3x3), WINO2_FWD above),
+    "off" (direct kernels everywhere).
+    direct_levels (1 | 2; default 2 for "bwd", "bwd_f2" and "off", 1 for "all"; MMH_DIRECT_LEVELS overrides the default): summation
     levels of the direct fp32 fprop with more than 64 output channels (mmh_set_option("conv_levels")).  Two levels - a fresh
     MFMA chain per 32-deep k-step, folded by vector adds - take the full-size Generator's output from 2.9e-6 to 1.1e-6 of
     float64 (PyTorch's fp32 on the CPU: 1.2e-6) and with it the parameter gradients from a median 2.2e-3 to 9.5e-4 (PyTorch:
     7.6e-4): at 256x256 the gradients' distance follows the FORWARD's (DESIGN 2.1).  The modes whose point is accuracy get it;
     the all-Winograd headline keeps the one-level direct kernels for its stride-2 convs (its forward error is the
     Winograd transforms')."""
-    global USE_WINOGRAD, WINOGRAD_FPROP
-    if mode not in ("all", "bwd", "off"):
-        raise ValueError(f"winograd mode {mode!r}: expected all | bwd | off")
-    USE_WINOGRAD, WINOGRAD_FPROP = mode != "off", mode != "bwd"
+    global USE_WINOGRAD, WINOGRAD_FPROP, WINO2_FWD
+    if mode not in ("all", "bwd", "bwd_f2", "off"):
+        raise ValueError(f"winograd mode {mode!r}: expected all | bwd | bwd_f2 | off")
+    USE_WINOGRAD, WINOGRAD_FPROP, WINO2_FWD = mode != "off", mode not in ("bwd", "bwd_f2"), mode == "bwd_f2"
     if direct_levels is None:
         direct_levels = int(os.environ.get("MMH_DIRECT_LEVELS", "2" if mode != "all" else "1"))
     L.call("mmh_set_option", b"conv_levels", 2 if int(direct_levels) == 2 else 1)
@@ -355,6 +364,14 @@ def _wino_tile(B, H, W_, Cin, Cout, k, stride, pad, bf16, op="fprop"):
     if H % 2 == 0 and W_ % 2 == 0 and H >= 4 and W_ >= 4 and Cin * Cout >= 256 * 256:
         return 2
     return 0
+
+
+def _wino2_fwd_ok(x, H, W_, Cin, Cout, k, stride, pad):
+    """the F(2x2,3x3) two-level forward of mode "bwd_f2" takes this fp32 conv (else: the direct kernel, as in "bwd").
+    The tile-2 transforms address dense NHWC tensors only, so a strided view stays on the direct kernel."""
+    return (WINO2_FWD and USE_WINOGRAD and not WINOGRAD_FPROP and k == 3 and stride == 1 and pad == 1
+            and H % 2 == 0 and W_ % 2 == 0 and H >= 4 and W_ >= 4 and Cin % 32 == 0 and Cout % 32 == 0 and Cout >= 64
+            and Cin * Cout >= WINO2_FWD_MIN and x.dtype == torch.float32 and x.is_contiguous())
 
 
 def wino_weights(w, tile, flip_transpose=False, bf16=False):
@@ -498,12 +515,13 @@ def _take_stats(x, peek=False):
 
 
 def _wino_conv(x, U, bias, Cout, reflect, act, tile, time_it=False, keep_V=False, bf16=False, want_stats=False,
-               fold=False, pro=None, levels=0):
+               fold=False, pro=None, levels=0, levels16=0):
     """input transform -> P batched GEMMs (one launch) -> output transform (+bias, activation).
     keep_V also returns the transformed input (the wgrad pass contracts exactly this tensor).
     bf16: V, U, M are bf16 (tile 2), the GEMMs run on the bf16 MFMA; x, y stay fp32.
     fold (tile 6, fp32): x is dy of a reflect-padded conv; tiles cover the padded domain and the
-    output transform folds the pad ring back (reflect is ignored)."""
+    output transform folds the pad ring back (reflect is ignored).
+    levels16 (tile 2, fp32): the 16 GEMMs through mmh_wino_gemm_levels16 with that many summation levels."""
     B, H, W_, Cin = x.shape
     P = (tile + 2) ** 2
     if fold:
@@ -527,7 +545,10 @@ def _wino_conv(x, U, bias, Cout, reflect, act, tile, time_it=False, keep_V=False
         L.call("mmh_wino_input", _ptr(x), B, H, W_, Cin, 2 if fold else int(bool(reflect)), tile, dt, _ptr(V), _stream())
     if timed:
         e0.record()
-    if levels and not bf16:
+    if levels16:
+        assert tile == 2 and not bf16
+        L.call("mmh_wino_gemm_levels16", _ptr(V), _ptr(U), _ptr(M), tiles, Cin, Cout, levels16, _stream())
+    elif levels and not bf16:
         L.call("mmh_wino_gemm_levels", _ptr(V), _ptr(U), _ptr(M), tiles, Cin, Cout, P, levels, _stream())
     else:
         L.call("mmh_wino_gemm", _ptr(V), _ptr(U), _ptr(M), tiles, Cin, Cout, P, dt, _stream())
@@ -674,6 +695,10 @@ def raw_conv_fprop(x, w, bias, stride, pad, reflect, act=L.ACT_NONE, bf16=False,
     wt = _wino_tile(B, H, W_, Cin, Cout, k, stride, pad, bf16)
     if wt:
         return raw_conv_fprop_wino(x, w, bias, reflect, act, wt, bf16=bf16)
+    if not bf16 and _wino2_fwd_ok(x, H, W_, Cin, Cout, k, stride, pad):
+        # mode "bwd_f2".  No statistics by-product at tile 2: the norm behind this conv runs its own statistics pass, as it
+        # does behind every conv that parks none
+        return _wino_conv(x, wino_weights(w, 2), bias, Cout, reflect, act, 2, levels16=2)
     d = conv_desc(B, H, W_, Cin, Cout, k, stride, pad, reflect)
     y = _empty((B, d.Ho, d.Wo, Cout), x)
     if USE_THIN and k == 7 and stride == 1 and pad == 3 and Cout == 4 and Cin % 4 == 0:

@@ -14,6 +14,7 @@ Differences, all deliberate:
   * conv biases that feed an InstanceNorm get their exact (zero) gradient by default instead of the reference's
     rounding noise (ops.EXACT_NULL_BIAS_GRAD; MMH_NULL_BIAS_GRAD=compute restores it; INTEGRATION.md §2b);
   * --fp32_exact_grads (addition): the gradient-exact fp32 hybrid, see ops.set_winograd_mode;
+  * --fp32_exact_fwd direct | wino2 (addition): that hybrid's forward kernels (wino2 = ops.set_winograd_mode("bwd_f2"));
   * --graph_step (addition): single-process training replays the whole iteration from a captured hipGraph
     (MMHandModel._optimize_parameters_graph);
   * three additions: --G_n_blocks (the reference hard-codes 9), --vgg_weights (file with
@@ -76,6 +77,10 @@ _BASE = [
                                      "dgrad / wgrad on Winograd F(6x6,3x3) - at 256x256 the parameter gradients a median 9.5e-4 "
                                      "from float64 (PyTorch's own fp32: 7.6e-4; the all-Winograd default: 3e-3 on this network's "
                                      "ill-conditioned gradients); = MMH_WINOGRAD=bwd")),
+    ("--fp32_exact_fwd", dict(type=str, default="direct", choices=["direct", "wino2"],
+                              help="with --fp32_exact_grads only: the forward of the eligible 3x3 stride-1 convs - direct: the "
+                                   "implicit-GEMM kernel with two-level summation; wino2: Winograd F(2x2,3x3) with the same "
+                                   "two-level summation in its 16 GEMMs (= MMH_WINOGRAD=bwd_f2); no effect on the 16-bit opt levels")),
     ("--graph_step", dict(action="store_true",
                           help="single process: capture one optimize_parameters() - forward, three backward passes, three Adam "
                                "steps - into a hipGraph after a few eager iterations and replay it (Adam step count / lr, dropout "
@@ -120,6 +125,15 @@ _TEST = [
 ]
 
 
+def check_exact_fwd(opt):
+    """--fp32_exact_fwd chooses the forward of the gradient-exact hybrid: without --fp32_exact_grads there is none"""
+    if getattr(opt, "fp32_exact_fwd", "direct") not in ("direct", "wino2"):
+        raise ValueError(f"--fp32_exact_fwd {opt.fp32_exact_fwd!r}: expected direct | wino2")
+    if getattr(opt, "fp32_exact_fwd", "direct") != "direct" and not getattr(opt, "fp32_exact_grads", False):
+        raise ValueError("--fp32_exact_fwd wino2 needs --fp32_exact_grads (it selects that hybrid's forward kernels)")
+    return opt
+
+
 class BaseOptions:
     isTrain = None
     _extra = []
@@ -137,6 +151,10 @@ class BaseOptions:
         if not self.initialized:
             self.initialize()
         opt = self.parser.parse_args(args)
+        try:
+            check_exact_fwd(opt)
+        except ValueError as e:
+            self.parser.error(str(e))
         opt.isTrain = self.isTrain
         import torch
         if opt.distributed:
