@@ -860,6 +860,46 @@ int mmh_image_metrics(const mmh_image_src* a, const mmh_image_src* b, int B, int
                       double c1, double c2, void* ws, size_t ws_bytes, double* out /* [B][3]: ssim, l1, mse */,
                       mmh_stream_t s);
 
+/* ---- PNG decode of a batch on the device (data/generic_dataset.py:140-149: the four cv2.imread calls per sample) ----------
+ * N zlib streams - each the concatenated IDAT payload of ONE 8-bit, colour type 2 (RGB), non-interlaced PNG of H x W pixels,
+ * which is what cv2.imwrite and PIL write for the prepared RHD / STB directories - are inflated (RFC 1950 / 1951: stored, fixed
+ * and dynamic blocks), checked against their Adler-32 trailer, unfiltered (PNG filter types 0 - 4) and written as the pixels
+ * cv2.imread returns, in one launch, one wave per image.
+ *   streams : device bytes, streams_bytes of them; image i's stream is [offsets[i], offsets[i + 1])
+ *   offsets : device int64 [N + 1], non-decreasing, inside [0, streams_bytes] (an image whose range is not gets
+ *             MMH_PNG_E_RANGE; nothing outside a valid range is ever read)
+ *   scratch : device bytes, N * H * (1 + 3 W): the filtered scanlines of every image
+ *   out     : device uint8 [N][H][W][3], B,G,R per pixel if bgr != 0 (cv2.imread's order), else R,G,B
+ *   status  : device int32 [N]: MMH_PNG_OK or the first error of that image (the enum below).  An image with a non-zero status
+ *             leaves its out slot undefined and does not disturb the other images of the launch.
+ * Host-side argument errors (N < 0, H or W < 1, H * (1 + 3 W) >= 2^31, a null pointer with N > 0) return non-zero before any
+ * launch.  The container (signature, IHDR, chunk CRCs) is the host's: mmhand_amd/png.py.                                     */
+enum {
+    MMH_PNG_OK = 0,
+    MMH_PNG_E_HEADER = 1,           /* zlib header: CM != 8, window > 32 KiB or FCHECK                                   */
+    MMH_PNG_E_DICT = 2,             /* preset dictionary flag                                                            */
+    MMH_PNG_E_TRUNCATED = 3,        /* the stream ends inside a block or the trailer                                     */
+    MMH_PNG_E_BLOCK_TYPE = 4,       /* reserved block type 3                                                             */
+    MMH_PNG_E_STORED_LEN = 5,       /* stored block: LEN != ~NLEN                                                        */
+    MMH_PNG_E_CODE_OVER = 6,        /* over-subscribed code lengths                                                      */
+    MMH_PNG_E_CODE_INCOMPLETE = 7,  /* incomplete code lengths (other than one single 1-bit code)                        */
+    MMH_PNG_E_REPEAT = 8,           /* code-length symbol 16 with no previous length                                     */
+    MMH_PNG_E_CODE_COUNT = 9,       /* more than 286 / 30 codes announced, or a repeat runs past them                    */
+    MMH_PNG_E_NO_EOB = 10,          /* no code for end-of-block                                                          */
+    MMH_PNG_E_SYMBOL = 11,          /* length symbol 286 / 287 or distance symbol 30 / 31                                */
+    MMH_PNG_E_BAD_CODE = 12,        /* a bit pattern no code of an (accepted) incomplete set has                         */
+    MMH_PNG_E_DISTANCE = 13,        /* a match reaches before the start of the output                                    */
+    MMH_PNG_E_OUTPUT_LONG = 14,     /* more than H * (1 + 3 W) bytes                                                     */
+    MMH_PNG_E_OUTPUT_SHORT = 15,    /* the final block ends with fewer                                                   */
+    MMH_PNG_E_TRAILING = 16,        /* bytes after the Adler-32 trailer                                                  */
+    MMH_PNG_E_ADLER = 17,           /* Adler-32 mismatch                                                                 */
+    MMH_PNG_E_FILTER = 18,          /* a scanline's filter byte is above 4                                               */
+    MMH_PNG_E_STEPS = 19,           /* the step bound of the decoder tripped (cannot happen: every step consumes input)  */
+    MMH_PNG_E_RANGE = 20            /* offsets[i] .. offsets[i + 1] is not a range of the stream buffer                  */
+};
+int mmh_png_decode_batch(const void* streams, int64_t streams_bytes, const int64_t* offsets, int N, int H, int W, void* scratch,
+                         void* out, int32_t* status, int bgr, mmh_stream_t s);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }

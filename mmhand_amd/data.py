@@ -12,7 +12,11 @@ mmh_pose_heatmaps.
 absent from this image) into pinned uint8 batches that travel to the device as they are; everything arithmetic the
 reference's loader workers do per sample on the CPU (normalise, depth = 256 G + R, / 700, 21 full-image Gaussians x 2)
 happens in ONE device kernel behind `MMHandModel.set_input` (mmh_decode_inputs).  The legacy pair-list format of
-data/mmhand_dataset.py (CSV pairs + .npy pose arrays) is not read."""
+data/mmhand_dataset.py (CSV pairs + .npy pose arrays) is not read.
+
+`HandFolderLoader(device_png=True)` (--device_png, MMH_DEVICE_PNG=1; off by default) moves the boundary from decoded pixels
+to the files' bytes: the threads only read the files, the batch's zlib streams go up as one pinned buffer and
+mmh_png_decode_batch (png.py) writes the same uint8 [B,H,W,3] BGR tensors."""
 import os
 import pickle
 import random
@@ -76,6 +80,14 @@ def _read_bgr(path):
     return np.ascontiguousarray(rgb[:, :, ::-1])
 
 
+def _read_bytes(path):
+    with open(path, "rb") as fh:
+        return fh.read()
+
+
+_IMAGE_KEYS = ("img1", "img2", "dep1", "dep2")
+
+
 class HandFolderLoader:
     """Iterable of RAW device batches over a prepared RHD / STB directory; `MMHandModel.set_input` decodes them on the
     device (keys img1, img2, dep1, dep2: uint8 [B,H,W,3] BGR as cv2.imread delivers them; uv1, uv2: float64 [B,21,2];
@@ -95,7 +107,7 @@ class HandFolderLoader:
         world size, rank r takes r, r + world, ...); the last batch may be short; iteration stops after
         `max_dataset_size` BATCHES (the reference compares the batch index with it)."""
 
-    def __init__(self, opt, device=None, decoded=False, threads=None):
+    def __init__(self, opt, device=None, decoded=False, threads=None, device_png=None):
         self.opt = opt
         self.root_dir = opt.dataroot
         if not self.root_dir or not os.path.isfile(os.path.join(self.root_dir, "annotation.pickle")):
@@ -131,6 +143,14 @@ class HandFolderLoader:
         self.threads = int(threads if threads is not None else (getattr(opt, "nThreads", 4) or 1))
         self.epoch = 0          # the reference never calls sampler.set_epoch: the permutation is the same every epoch
         self.name = type(self).__name__
+        # opt-in: PNG bytes to the device (png.py).  Two buffer sets take turns, so a batch's raw tensors stay valid until the
+        # loader has yielded two more; `png_fallbacks` lists (path, reason) of every file PIL decoded instead
+        if device_png is None:
+            device_png = bool(getattr(opt, "device_png", False)) or os.environ.get("MMH_DEVICE_PNG", "0") == "1"
+        self.device_png = bool(device_png)
+        self.png_fallbacks = []
+        self._png_sets = self._png_stream = self._png_prev = None
+        self._png_turn = 0
 
     def _get_src_tgt(self, ratio, data, sort_fn):
         assert len(data) > 0, "no images listed in annotation.pickle for this --dataset"
@@ -181,13 +201,24 @@ class HandFolderLoader:
         uv2 = np.asarray(a2["uv_coord"], dtype=np.float64).reshape(21, 2)
         z1 = np.expand_dims(np.asarray(a1["depth"], dtype=np.float64), -1) / 700.0 * 255
         z2 = np.expand_dims(np.asarray(a2["depth"], dtype=np.float64), -1) / 700.0 * 255
+        if self.device_png:
+            return dict(img1=_read_bytes(h_1), img2=_read_bytes(h_2), dep1=_read_bytes(h_1.replace("color", "depth")),
+                        dep2=_read_bytes(h_2.replace("color", "depth")), uv1=uv1, uv2=uv2,
+                        C1=np.concatenate([uv1, z1], axis=-1), C2=np.concatenate([uv2, z2], axis=-1), H1_path=h_1, H2_path=h_2)
         return dict(img1=_read_bgr(h_1), img2=_read_bgr(h_2), dep1=_read_bgr(h_1.replace("color", "depth")),
                     dep2=_read_bgr(h_2.replace("color", "depth")), uv1=uv1, uv2=uv2,
                     C1=np.concatenate([uv1, z1], axis=-1), C2=np.concatenate([uv2, z2], axis=-1), H1_path=h_1, H2_path=h_2)
 
     def _collate(self, samples):
         out = {}
-        for k in ("img1", "img2", "dep1", "dep2", "uv1", "uv2", "C1", "C2"):
+        if self.device_png:
+            from .png import PngBatchDecoder
+            if self._png_sets is None:
+                self._png_sets = [PngBatchDecoder(self.device), PngBatchDecoder(self.device)]
+            dec = self._png_sets[self._png_turn % 2]
+            self._png_turn += 1
+            out["_png"] = (dec, dec.pack([s[k] for k in _IMAGE_KEYS for s in samples]))
+        for k in ("uv1", "uv2", "C1", "C2") if self.device_png else ("img1", "img2", "dep1", "dep2", "uv1", "uv2", "C1", "C2"):
             t = torch.from_numpy(np.stack([s[k] for s in samples]))
             out[k] = t.pin_memory() if torch.cuda.is_available() else t
         out["H1_path"] = [s["H1_path"] for s in samples]
@@ -209,8 +240,30 @@ class HandFolderLoader:
                 nxt = [pool.submit(self.load_sample, i) for i in groups[gi + 1]] if gi + 1 < len(groups) else []
                 yield self._collate([f.result() for f in cur])
 
+    def _png_to_device(self, hb):
+        """upload + mmh_png_decode_batch on the loader's own stream (beside whatever the consumer still has queued), the
+        four image tensors as views of the set's output buffer"""
+        dec, plan = hb["_png"]
+        cur = torch.cuda.current_stream(self.device)
+        if self._png_stream is None:
+            self._png_stream = torch.cuda.Stream(self.device)
+        if self._png_prev is not None:
+            # everything queued before the previous batch was handed out - the consumers of the batch this set held - is done
+            self._png_stream.wait_event(self._png_prev)
+        self._png_prev = torch.cuda.Event()
+        self._png_prev.record(cur)
+        pix, report = dec.launch(plan, bgr=True, stream=self._png_stream)
+        cur.wait_stream(self._png_stream)
+        B = len(hb["H1_path"])
+        for i, reason in report:
+            path = (hb["H1_path"] if i // B in (0, 2) else hb["H2_path"])[i % B]
+            self.png_fallbacks.append((path.replace("color", "depth") if i // B >= 2 else path, reason))
+        return {k: pix[j * B:(j + 1) * B] for j, k in enumerate(_IMAGE_KEYS)}
+
     def to_device(self, hb):
-        out = {k: (v.to(self.device, non_blocking=True) if torch.is_tensor(v) else v) for k, v in hb.items()}
+        out = {k: (v.to(self.device, non_blocking=True) if torch.is_tensor(v) else v) for k, v in hb.items() if k != "_png"}
+        if "_png" in hb:
+            out = {**self._png_to_device(hb), **out}
         if not self.decoded:
             return out
         xh1, xh2, xp, xd = ops.decode_inputs(out["img1"], out["img2"], out["dep1"], out["dep2"], out["uv1"], out["uv2"])

@@ -44,6 +44,7 @@ def build_parser():
     p.add_argument("--batchSize", type=int, default=16)
     p.add_argument("--bf16", action="store_true", help="the generator's 16-bit (bf16 MFMA) inference mode")
     p.add_argument("--gpu", type=int, default=0)
+    p.add_argument("--device_png", action="store_true", help="decode the dataset's PNGs on the device (= MMH_DEVICE_PNG=1)")
     p.add_argument("--window", type=int, default=11, help="SSIM window, odd, 3 .. 15 (the reference's default 11)")
     p.add_argument("--results_json", default=None,
                    help="default: <checkpoints_dir>/<name>/eval_<which_epoch>_<dataset>.json, or <generated>/eval_<dataset>.json")
@@ -84,6 +85,7 @@ def _opt(args):
     opt = default_train_opt(batchSize=args.batchSize, local_rank=args.gpu, isTrain=False)
     opt.dataroot, opt.dataset, opt.augmentation_ratio, opt.distributed = (args.dataroot, args.dataset,
                                                                           args.augmentation_ratio, False)
+    opt.device_png = bool(getattr(args, "device_png", False))
     return opt
 
 

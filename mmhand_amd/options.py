@@ -85,6 +85,10 @@ _BASE = [
                           help="single process: capture one optimize_parameters() - forward, three backward passes, three Adam "
                                "steps - into a hipGraph after a few eager iterations and replay it (Adam step count / lr, dropout "
                                "salt and image-pool decisions live behind device pointers); = MMH_GRAPH_STEP=1")),
+    ("--device_png", dict(action="store_true",
+                          help="with --dataroot: the loader uploads the PNG files' bytes and the device inflates and unfilters "
+                               "them (mmh_png_decode_batch); files that are not 8-bit RGB non-interlaced go through PIL; "
+                               "= MMH_DEVICE_PNG=1")),
 ]
 _TRAIN = [
     ("--display_freq", dict(type=int, default=100)),
