@@ -820,6 +820,21 @@ int mmh_decode_inputs(const void* img1, const void* img2, const void* dep1,
                       const void* dep2, const void* uv1, const void* uv2,
                       int B, int H, int W, double sigma, void* x_h1, void* x_h2,
                       void* x_p, void* x_d, mmh_stream_t s);
+/* The same pass with the resize inside it: sources uint8 [B,Hs,Ws,3] BGR at the files'
+ * size, the four outputs (layouts as above) at Ho x Wo.  Bilinear with half-pixel centres
+ * and edge clamp, per output pixel: sx = (x + 0.5) * Ws / Wo - 0.5 clamped below at 0,
+ * x0 = floor(sx), x1 = min(x0 + 1, Ws - 1), weight sx - x0, the same in y - what
+ * F.interpolate(mode="bilinear", align_corners=False, antialias=False) samples; it up- and
+ * down-scales, with independent ratios in H and W.  The four taps are combined in float64
+ * from the raw bytes (colour per channel, depth as 256*G + R per tap), the result goes
+ * through the normalisation above in float64, and the store is the only rounding.
+ * uv1, uv2 are joints ALREADY scaled to the output grid, u' = (u + 0.5) * Wo / Ws - 0.5,
+ * v' = (v + 0.5) * Ho / Hs - 0.5: the pose maps are the Gaussians of mmh_decode_inputs on
+ * output pixel coordinates (sigma is not scaled).  The outputs must be 16-byte aligned.  */
+int mmh_decode_inputs_resized(const void* img1, const void* img2, const void* dep1,
+                              const void* dep2, const void* uv1, const void* uv2,
+                              int B, int Hs, int Ws, int Ho, int Wo, double sigma,
+                              void* x_h1, void* x_h2, void* x_p, void* x_d, mmh_stream_t s);
 
 /* ---- data-parallel gradient all-reduce (apex DistributedDataParallel behind
  * models/MMHandModel.py:109-116; reduce_tensor :381-384) -------------------------

@@ -3,6 +3,9 @@
     python -m mmhand_amd.aug <checkpoint_name> <dataroot> <dst_dir> <rhd|stb> <ratio> <device>     (the reference's argv, aug.py:16)
     python -m mmhand_amd.aug <checkpoint_name> <dst_dir> [n_batches] [batch] [device]              (synthetic batches)
 
+`--resize_inputs N` (an addition, anywhere on the first form's command line): the pairs reach the generator at N x N whatever
+size the files hold - the resize is part of the device's decode pass - and the PNGs are written at that size.
+
 The first form reads the reference's prepared directory (data.HandFolderLoader: annotation.pickle + colour / depth PNGs,
 the generation side of the augmentation_ratio split, batch size 1, decoded on the device) and writes each generated image
 to <dst>/<folder of the TARGET image>/<its file name> (aug.py:66-71).
@@ -13,6 +16,7 @@ captures the forward in a hipGraph and writes the generated images ((x*0.5+0.5)*
 then cv2.imwrite) as PNG files via PIL (cv2 is absent here; cv2.imwrite of a BGR float array
 rounds to nearest uint8 and stores RGB-ordered PNG pixels, which is what PIL is given) or, without
 PIL, as .npy arrays."""
+import argparse
 import os
 import sys
 
@@ -22,12 +26,21 @@ import torch
 from .data import HandFolderLoader, SyntheticHandLoader
 from .inference import InferenceGenerator
 from .networks import Generator
-from .options import default_train_opt
+from .options import check_resize_inputs, default_train_opt
 
 
-def main(argv, ngf=64, n_blocks=9, size=None):
+def main(argv, ngf=64, n_blocks=9, size=None, resize_inputs=0):
     """argv as the reference's aug.py; ngf / n_blocks / size are the reference's hard-coded 64 / 9 / 256 (aug.py:31-39),
-    keyword-overridable so that a test can drive the whole path on a small checkpoint."""
+    keyword-overridable so that a test can drive the whole path on a small checkpoint.  resize_inputs = N, or
+    `--resize_inputs N` in argv: the prepared directory's pairs are decoded to N x N (options.check_resize_inputs)."""
+    argv = list(argv)
+    if "--resize_inputs" in argv:
+        i = argv.index("--resize_inputs")
+        if i + 1 >= len(argv) or not argv[i + 1].lstrip("-").isdigit():
+            raise ValueError("--resize_inputs: expected an integer")
+        resize_inputs = int(argv[i + 1])
+        del argv[i:i + 2]
+    check_resize_inputs(argparse.Namespace(resize_inputs=resize_inputs))
     ckp = argv[0]
     real = len(argv) == 6 and argv[3] in ("rhd", "stb")        # _, ckp, dataroot, DST, dataset, ratio, device = sys.argv
     if real:
@@ -45,7 +58,7 @@ def main(argv, ngf=64, n_blocks=9, size=None):
                       n_blocks=n_blocks)
     model.load_state_dict(weights)
     gen = InferenceGenerator(model.to(dev).eval(), use_graph=True)
-    opt = default_train_opt(batchSize=batch, local_rank=device, isTrain=False)
+    opt = default_train_opt(batchSize=batch, local_rank=device, isTrain=False, resize_inputs=resize_inputs)
     if real:
         # aug.py:18-26: isTrain False, batchSize 1, not distributed; the loader hands decoded NCHW views
         opt.dataroot, opt.dataset, opt.augmentation_ratio, opt.distributed = dataroot, dataset, ratio, False

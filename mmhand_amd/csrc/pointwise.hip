@@ -1951,6 +1951,86 @@ __global__ void decode_inputs_kernel(const uint8_t* __restrict__ img1, const uin
     }
 }
 
+// The same pass writing the network's size Ho x Wo from sources of the files' size Hs x Ws (mmh_decode_inputs_resized):
+// bilinear, half-pixel centres, edge clamp - F.interpolate(mode="bilinear", align_corners=False, antialias=False).  The four
+// taps are combined in double from the raw bytes and the result goes through norm_u8's / depth_u8's formula in double: one
+// rounding, at the store.  The joints arrive scaled to the output grid, so the pose maps are heat() on output pixels.
+// One float4 per lane, 15 lanes per output pixel (x_h1, x_h2, 2 of x_d, 11 of x_p = 240 bytes), so that a wave's stores
+// into x_p are contiguous.
+struct ResizeTap { int i0, i1; double w; };
+__device__ __forceinline__ ResizeTap resize_tap(int o, int n_src, int n_out) {
+    double s = ((double)o + 0.5) * (double)n_src / (double)n_out - 0.5;
+    if (s < 0.0) s = 0.0;
+    ResizeTap t;
+    t.i0 = min((int)s, n_src - 1);          // s >= 0: the cast is the floor
+    t.i1 = min(t.i0 + 1, n_src - 1);
+    t.w = s - (double)t.i0;
+    return t;
+}
+__device__ __forceinline__ double lerp2(double v00, double v01, double v10, double v11, double wx, double wy) {
+    return (1.0 - wy) * ((1.0 - wx) * v00 + wx * v01) + wy * ((1.0 - wx) * v10 + wx * v11);
+}
+__device__ __forceinline__ float norm_f64(double v) { return (float)((v / 255.0 - 0.5) / 0.5); }
+__device__ __forceinline__ double depth_raw(const uint8_t* p) { return 256.0 * (double)p[1] + (double)p[2]; }
+__device__ __forceinline__ float depth_f64(double d) { return (float)(((d / 700.0) - 0.5) / 0.5); }
+
+constexpr int DECODE_LANES = 15;
+__global__ void decode_inputs_resized_kernel(const uint8_t* __restrict__ img1, const uint8_t* __restrict__ img2,
+                                             const uint8_t* __restrict__ dep1, const uint8_t* __restrict__ dep2,
+                                             const double* __restrict__ uv1, const double* __restrict__ uv2,
+                                             int B, int Hs, int Ws, int Ho, int Wo, double sigma,
+                                             float* __restrict__ xh1, float* __restrict__ xh2,
+                                             float* __restrict__ xp, float* __restrict__ xd) {
+    const int64_t total = (int64_t)B * Ho * Wo * DECODE_LANES;
+    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (; i < total; i += stride) {
+        const int q = (int)(i % DECODE_LANES);
+        const int64_t px = i / DECODE_LANES;
+        const int x = (int)(px % Wo);
+        const int64_t t = px / Wo;
+        const int y = (int)(t % Ho);
+        const int b = (int)(t / Ho);
+        if (q >= 4) {
+            // pose maps: channels 4 (q - 4) .. + 3 of 44 (P1 in 0..20, P2 in 21..41, 42 and 43 zero)
+            const double* u1 = uv1 + (int64_t)b * 42;
+            const double* u2 = uv2 + (int64_t)b * 42;
+            float v[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int c = (q - 4) * 4 + e;
+                v[e] = c < 21 ? heat((double)x, (double)y, u1[2 * c], u1[2 * c + 1], sigma)
+                     : c < 42 ? heat((double)x, (double)y, u2[2 * (c - 21)], u2[2 * (c - 21) + 1], sigma) : 0.f;
+            }
+            st4(xp, px * 11 + (q - 4), make_float4(v[0], v[1], v[2], v[3]));
+            continue;
+        }
+        const ResizeTap tx = resize_tap(x, Ws, Wo), ty = resize_tap(y, Hs, Ho);
+        const int64_t row0 = ((int64_t)b * Hs + ty.i0) * Ws, row1 = ((int64_t)b * Hs + ty.i1) * Ws;
+        const int64_t o00 = (row0 + tx.i0) * 3, o01 = (row0 + tx.i1) * 3, o10 = (row1 + tx.i0) * 3, o11 = (row1 + tx.i1) * 3;
+        if (q < 2) {
+            // images: BGR uint8 -> RGB normalised
+            const uint8_t* p = q == 0 ? img1 : img2;
+            float c[3];
+#pragma unroll
+            for (int e = 0; e < 3; ++e)
+                c[e] = norm_f64(lerp2((double)p[o00 + e], (double)p[o01 + e], (double)p[o10 + e], (double)p[o11 + e], tx.w, ty.w));
+            st4(q == 0 ? xh1 : xh2, px, make_float4(c[2], c[1], c[0], 0.f));
+        } else {
+            // depth: 256*G + R per tap (BGR order: index 1 = G, 2 = R), interpolated, then / 700 and normalised
+            const float d2 = depth_f64(lerp2(depth_raw(dep2 + o00), depth_raw(dep2 + o01), depth_raw(dep2 + o10),
+                                             depth_raw(dep2 + o11), tx.w, ty.w));
+            if (q == 2) {
+                const float d1 = depth_f64(lerp2(depth_raw(dep1 + o00), depth_raw(dep1 + o01), depth_raw(dep1 + o10),
+                                                 depth_raw(dep1 + o11), tx.w, ty.w));
+                st4(xd, px * 2, make_float4(d1, d1, d1, d2));
+            } else {
+                st4(xd, px * 2 + 1, make_float4(d2, d2, 0.f, 0.f));
+            }
+        }
+    }
+}
+
 // ------------------------------------------------------------------ bf16 weight copies
 // T = __bf16 or _Float16
 template <typename T>
@@ -2918,6 +2998,23 @@ int mmh_decode_inputs(const void* img1, const void* img2, const void* dep1, cons
                        static_cast<const double*>(uv2), B, H, W, sigma, static_cast<float*>(x_h1),
                        static_cast<float*>(x_h2), static_cast<float*>(x_p), static_cast<float*>(x_d));
     return mmh::check_launch("decode_inputs");
+}
+
+int mmh_decode_inputs_resized(const void* img1, const void* img2, const void* dep1, const void* dep2,
+                              const void* uv1, const void* uv2, int B, int Hs, int Ws, int Ho, int Wo, double sigma,
+                              void* x_h1, void* x_h2, void* x_p, void* x_d, mmh_stream_t s) {
+    MMH_REQUIRE(img1 && img2 && dep1 && dep2 && uv1 && uv2 && x_h1 && x_h2 && x_p && x_d,
+                "mmh_decode_inputs_resized: NULL buffer");
+    MMH_REQUIRE(B > 0 && Hs > 0 && Ws > 0 && Ho > 0 && Wo > 0 && sigma > 0, "mmh_decode_inputs_resized: bad shape");
+    MMH_REQUIRE(((reinterpret_cast<uintptr_t>(x_h1) | reinterpret_cast<uintptr_t>(x_h2) | reinterpret_cast<uintptr_t>(x_p) |
+                  reinterpret_cast<uintptr_t>(x_d)) & 15) == 0, "mmh_decode_inputs_resized: outputs must be 16-byte aligned");
+    hipLaunchKernelGGL(decode_inputs_resized_kernel, dim3(grid_for((int64_t)B * Ho * Wo * DECODE_LANES)), dim3(TPB), 0,
+                       mmh::as_stream(s), static_cast<const uint8_t*>(img1),
+                       static_cast<const uint8_t*>(img2), static_cast<const uint8_t*>(dep1),
+                       static_cast<const uint8_t*>(dep2), static_cast<const double*>(uv1),
+                       static_cast<const double*>(uv2), B, Hs, Ws, Ho, Wo, sigma, static_cast<float*>(x_h1),
+                       static_cast<float*>(x_h2), static_cast<float*>(x_p), static_cast<float*>(x_d));
+    return mmh::check_launch("decode_inputs_resized");
 }
 
 int mmh_prep_weights_bf16(const void* w, int taps, int Cin, int Cout, void* w_plain, void* w_t,

@@ -25,6 +25,7 @@ import numpy as np
 import torch
 
 from . import ops
+from .options import check_resize_inputs
 
 
 class SyntheticHandLoader:
@@ -92,7 +93,8 @@ class HandFolderLoader:
     """Iterable of RAW device batches over a prepared RHD / STB directory; `MMHandModel.set_input` decodes them on the
     device (keys img1, img2, dep1, dep2: uint8 [B,H,W,3] BGR as cv2.imread delivers them; uv1, uv2: float64 [B,21,2];
     C1, C2: float64 [B,21,3] = (u, v, depth / 700 * 255); H1_path, H2_path).  `decoded=True` yields the reference's own
-    keys instead (H1, P1, D1, ... as NCHW fp32 views of the decoded buffers) for callers that want tensors.
+    keys instead (H1, P1, D1, ... as NCHW fp32 views of the decoded buffers) for callers that want tensors; with
+    --resize_inputs N those come out at N x N (the resize is part of the decode kernel's pass, ops.decode_inputs).
 
     Mirrors, by file:line of the reference:
       * image lists: RHD - every image of annotation folder "color", sorted by the integer file stem
@@ -109,6 +111,9 @@ class HandFolderLoader:
 
     def __init__(self, opt, device=None, decoded=False, threads=None, device_png=None):
         self.opt = opt
+        # --resize_inputs N: the decoded form (decoded=True) comes out at N x N (joints in C1 / C2 scaled with it); the raw
+        # form always travels at the files' size - MMHandModel.set_input resizes inside its decode pass
+        self.out_size = check_resize_inputs(opt) or None
         self.root_dir = opt.dataroot
         if not self.root_dir or not os.path.isfile(os.path.join(self.root_dir, "annotation.pickle")):
             raise FileNotFoundError(f"--dataroot {self.root_dir!r}: no annotation.pickle (the directory create_RHD_DB.py / "
@@ -266,10 +271,14 @@ class HandFolderLoader:
             out = {**self._png_to_device(hb), **out}
         if not self.decoded:
             return out
-        xh1, xh2, xp, xd = ops.decode_inputs(out["img1"], out["img2"], out["dep1"], out["dep2"], out["uv1"], out["uv2"])
+        src = tuple(out["img1"].shape[1:3])
+        dst = ops.resize_size(self.out_size, src)
+        xh1, xh2, xp, xd = ops.decode_inputs(out["img1"], out["img2"], out["dep1"], out["dep2"], out["uv1"], out["uv2"],
+                                             out_size=dst)
+        c1, c2 = (out[k] if dst is None else ops.resize_joints(out[k], src, dst) for k in ("C1", "C2"))
         v = ops.nhwc_to_nchw_view
         return {"H1": v(xh1, 3), "H2": v(xh2, 3), "P1": v(xp)[:, :21], "P2": v(xp)[:, 21:42], "D1": v(xd)[:, :3],
-                "D2": v(xd)[:, 3:6], "C1": out["C1"], "C2": out["C2"], "H1_path": out["H1_path"], "H2_path": out["H2_path"]}
+                "D2": v(xd)[:, 3:6], "C1": c1, "C2": c2, "H1_path": out["H1_path"], "H2_path": out["H2_path"]}
 
     def __iter__(self):
         for hb in self.host_batches():

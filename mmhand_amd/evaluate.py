@@ -6,11 +6,14 @@ scores each output against its target image H2:
 
     python -m mmhand_amd.evaluate --name CKP [--checkpoints_dir checkpoints] [--which_epoch latest] --dataroot DIR
         --dataset rhd|stb [--augmentation_ratio R] [--batchSize 16] [--bf16] [--gpu 0] [--window 11]
-        [--results_json PATH] [--per_image_csv PATH]
+        [--resize_inputs N] [--results_json PATH] [--per_image_csv PATH]
 
 Directory mode - scores the PNGs aug.py wrote (<DIR>/<folder of the target>/<name>) against the target colour PNGs:
 
     python -m mmhand_amd.evaluate --generated DIR --dataroot DIR --dataset rhd|stb [--augmentation_ratio R] ...
+
+`--resize_inputs N`: the pairs are decoded to N x N inside the device's decode pass (ops.decode_inputs; what `train` and `aug`
+do under the same flag); directory mode then expects N x N PNGs and scores them against the targets decoded at that size.
 
 Both print one summary line (SSIM_avg, SSIM_std, L1_avg, PSNR_avg, n) and write it with the options used as JSON."""
 import argparse
@@ -45,6 +48,8 @@ def build_parser():
     p.add_argument("--bf16", action="store_true", help="the generator's 16-bit (bf16 MFMA) inference mode")
     p.add_argument("--gpu", type=int, default=0)
     p.add_argument("--device_png", action="store_true", help="decode the dataset's PNGs on the device (= MMH_DEVICE_PNG=1)")
+    p.add_argument("--resize_inputs", type=int, default=0,
+                   help="score at N x N: the dataset's images resized inside the device's decode pass (0 = the files' size)")
     p.add_argument("--window", type=int, default=11, help="SSIM window, odd, 3 .. 15 (the reference's default 11)")
     p.add_argument("--results_json", default=None,
                    help="default: <checkpoints_dir>/<name>/eval_<which_epoch>_<dataset>.json, or <generated>/eval_<dataset>.json")
@@ -86,6 +91,7 @@ def _opt(args):
     opt.dataroot, opt.dataset, opt.augmentation_ratio, opt.distributed = (args.dataroot, args.dataset,
                                                                           args.augmentation_ratio, False)
     opt.device_png = bool(getattr(args, "device_png", False))
+    opt.resize_inputs = int(getattr(args, "resize_inputs", 0) or 0)
     return opt
 
 
@@ -117,10 +123,22 @@ def _read_generated(path):
     raise SystemExit(f"--generated: {path} is missing (aug.py writes <DIR>/<folder of the target>/<name>)")
 
 
+def _targets_at(ref, size):
+    """uint8 [B,H,W,3] BGR target images -> fp32 [B,3,N,N] RGB in [-1, 1] as the device's decode pass delivers them at
+    N x N (the colour lanes of ops.decode_inputs; its other inputs are not looked at)"""
+    from . import ops
+    uv = torch.zeros((ref.shape[0], 21, 2), dtype=torch.float64, device=ref.device)
+    xh, _, _, _ = ops.decode_inputs(ref, ref, ref, ref, uv, uv, out_size=size)
+    return ops.nhwc_to_nchw_view(xh, 3)
+
+
 def _score_directory(args, dev):
     from .data import HandFolderLoader, _read_bgr
     loader = HandFolderLoader(_opt(args), device=dev)
-    meter = QualityMeter("u8_bgr_hwc", args.window)
+    size = loader.out_size
+    # at the files' size both sides are bytes; at --resize_inputs N the targets are the decode pass's fp32 images, and the
+    # PNGs' bytes are mapped to the same [-1, 1] range
+    meter = QualityMeter("pm1" if size else "u8_bgr_hwc", args.window)
     idx = loader.indices()
     for i in range(0, len(idx), args.batchSize):
         tgts = [loader.image_target[j] for j in idx[i:i + args.batchSize]]
@@ -128,8 +146,15 @@ def _score_directory(args, dev):
         gen = [_read_generated(os.path.join(args.generated, *t.split("/")[-2:])) for t in tgts]
         ref = [_read_bgr(t) for t in tgts]
         for g, r, t in zip(gen, ref, tgts):
-            if g.shape != r.shape:
-                raise SystemExit(f"--generated: {t}: generated image {g.shape} vs target {r.shape}")
+            want = (size, size, 3) if size else r.shape
+            if g.shape != want:
+                raise SystemExit(f"--generated: {t}: generated image {g.shape} vs target {want}")
+        if size:
+            g8 = torch.from_numpy(np.stack(gen)).to(dev)
+            pred = (g8.flip(-1).permute(0, 3, 1, 2).float() / 255.0 - 0.5) / 0.5
+            meter.feed(pred, _targets_at(torch.from_numpy(np.stack(ref)).to(dev).contiguous(), size),
+                       [{"target": t, "source": s} for t, s in zip(tgts, srcs)])
+            continue
         meter.feed(torch.from_numpy(np.stack(gen)).to(dev), torch.from_numpy(np.stack(ref)).to(dev),
                    [{"target": t, "source": s} for t, s in zip(tgts, srcs)])
     return meter, {}
@@ -142,6 +167,8 @@ def main(argv=None):
         parser.error(f"--window {args.window}: the SSIM window is odd, from 3 to 15")
     if args.batchSize < 1:
         parser.error("--batchSize must be >= 1")
+    from .options import check_resize_inputs
+    check_resize_inputs(args)
     ckpt = None
     if args.name:
         ckpt = os.path.join(args.checkpoints_dir, args.name, f"{args.which_epoch}_net_netG.pth")

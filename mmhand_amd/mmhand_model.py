@@ -23,7 +23,7 @@ from . import lib as L
 from . import ops
 from .networks import Discriminator, Generator, VGGHead, discriminators_lockstep
 from .ops import pad4
-from .options import check_exact_fwd
+from .options import check_exact_fwd, check_resize_inputs
 
 
 MERGE_D_PASSES = os.environ.get("MMH_MERGE_D", "1") != "0"
@@ -326,6 +326,7 @@ class MMHandModel(torch.nn.Module):
         self.world = dist.get_world_size() if (getattr(opt, "distributed", False)
                                                and dist.is_initialized()) else 1
         check_exact_fwd(opt)
+        self.resize_inputs = check_resize_inputs(opt)      # --resize_inputs N: raw batches are decoded to N x N (set_input_raw)
         if getattr(opt, "fp32_exact_grads", False):
             # process-wide, like MMH_WINOGRAD=bwd | bwd_f2 (one model family per process)
             ops.set_winograd_mode("bwd_f2" if getattr(opt, "fp32_exact_fwd", "direct") == "wino2" else "bwd")
@@ -537,6 +538,12 @@ class MMHandModel(torch.nn.Module):
                     v.record_stream(cur)
             else:
                 t = {k: input[k].contiguous() for k in raw}
+            if "C1" in input and "C2" in input:
+                # (u, v, depth) of the joints on the grid the networks see: scaled with the images under --resize_inputs
+                src, dst = tuple(t["img1"].shape[1:3]), ops.resize_size(self.resize_inputs, t["img1"].shape[1:3])
+                self.input_C1, self.input_C2 = (input[k].to(dev, non_blocking=True) if dst is None else
+                                                ops.resize_joints(input[k].to(dev, non_blocking=True), src, dst)
+                                                for k in ("C1", "C2"))
             return self.set_input_raw(*[t[k] for k in raw], paths=(input["H1_path"], input["H2_path"]) if "H1_path" in input else None)
         keys = ("H1", "P1", "D1", "H2", "P2", "D2")
         if dev.type == "cuda" and any(not input[k].is_cuda for k in keys):
@@ -594,9 +601,13 @@ class MMHandModel(torch.nn.Module):
         """Input straight from decoded files: uint8 BGR images / depth PNGs [B,H,W,3] and float64
         joints [B,21,2] on the device.  One kernel (mmh_decode_inputs) does what the reference's
         loader workers do per sample on the CPU (data/generic_dataset.py:133-180) and writes the
-        stems' NHWC buffers directly; the NCHW tensors the rest of the API exposes are views."""
+        stems' NHWC buffers directly; the NCHW tensors the rest of the API exposes are views.
+        --resize_inputs N: the same kernel pass writes N x N (ops.decode_inputs(out_size=...)); the raw batch stays at the
+        files' size.  Under --graph_step the decode runs in front of the replay, as it does without the flag: the captured
+        iteration reads the N x N buffers it is copied into."""
+        size = self.resize_inputs or None
         if getattr(self, "_graph_state", "off") == "replay":
-            xh1, xh2, xp, xd = ops.decode_inputs(img1, img2, dep1, dep2, uv1, uv2)
+            xh1, xh2, xp, xd = ops.decode_inputs(img1, img2, dep1, dep2, uv1, uv2, out_size=size)
             v, o = ops.nhwc_to_nchw_view, self.opt
             d = {"H1": v(xh1, o.H_input_nc), "H2": v(xh2, o.H_input_nc), "P1": v(xp)[:, : o.P_input_nc],
                  "P2": v(xp)[:, o.P_input_nc: 2 * o.P_input_nc], "D1": v(xd)[:, : o.D_input_nc],
@@ -606,7 +617,7 @@ class MMHandModel(torch.nn.Module):
             return self.set_input(d)
         for old in (getattr(self, "x_H1", None), getattr(self, "x_P", None), getattr(self, "x_D", None)):
             ops.pack_twin_drop(old)         # 16-bit copies a set_input() parked for the previous batch
-        self.x_H1, self.x_H2, self.x_P, self.x_D = ops.decode_inputs(img1, img2, dep1, dep2, uv1, uv2)
+        self.x_H1, self.x_H2, self.x_P, self.x_D = ops.decode_inputs(img1, img2, dep1, dep2, uv1, uv2, out_size=size)
         v = ops.nhwc_to_nchw_view
         o = self.opt
         self.input_H1, self.input_H2 = v(self.x_H1, o.H_input_nc), v(self.x_H2, o.H_input_nc)

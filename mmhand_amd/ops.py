@@ -3188,15 +3188,54 @@ def map_to_cord(maps, threshold=0.1):
     return out
 
 
-def decode_inputs(img1, img2, dep1, dep2, uv1, uv2, sigma=6.0):
+def resize_size(out_size, src):
+    """(Ho, Wo) of an `out_size` (None / 0 = off, an int N = N x N, a pair) for sources of size src = (Hs, Ws); None when
+    nothing is to be resized"""
+    if not out_size:
+        return None
+    Ho, Wo = (int(out_size), int(out_size)) if isinstance(out_size, int) else (int(out_size[0]), int(out_size[1]))
+    if Ho <= 0 or Wo <= 0:
+        raise ValueError(f"out_size {out_size!r}: positive sizes expected")
+    return None if (Ho, Wo) == (int(src[0]), int(src[1])) else (Ho, Wo)
+
+
+def resize_joints(uv, src, dst):
+    """Joints [..., 2 or 3] = (u, v[, depth]) of an Hs x Ws image on the grid of its Ho x Wo resize (half-pixel centres, the
+    map mmh_decode_inputs_resized samples with): u' = (u + 0.5) Wo / Ws - 0.5, v' = (v + 0.5) Ho / Hs - 0.5, in float64;
+    further components (C1 / C2's depth) unchanged.  THE place the joints are scaled."""
+    (Hs, Ws), (Ho, Wo) = src, dst
+    out = uv.to(torch.float64).clone()
+    out[..., 0] = (out[..., 0] + 0.5) * float(Wo) / float(Ws) - 0.5
+    out[..., 1] = (out[..., 1] + 0.5) * float(Ho) / float(Hs) - 0.5
+    return out
+
+
+def decode_inputs(img1, img2, dep1, dep2, uv1, uv2, sigma=6.0, out_size=None):
     """On-device input pipeline (data/generic_dataset.py:133-180): uint8 BGR images + depth PNGs
-    [B,H,W,3] and float64 joints [B,21,2] -> the stems' NHWC buffers (x_H1, x_H2, x_P, x_D)."""
+    [B,H,W,3] and float64 joints [B,21,2] -> the stems' NHWC buffers (x_H1, x_H2, x_P, x_D).
+
+    out_size = (Ho, Wo) other than (H, W): the same buffers at Ho x Wo in the same single pass
+    (mmh_decode_inputs_resized: bilinear, half-pixel centres, edge clamp = F.interpolate(mode="bilinear",
+    align_corners=False), taps combined in float64 from the raw bytes); the joints are scaled to the output grid here
+    (resize_joints) and sigma stays what it is - 6 at every size, as the synthetic 512x512 configuration already has it.
+    None, or the sources' own size, is the plain call."""
     B, H, W_, _ = img1.shape
     for t in (img1, img2, dep1, dep2):
         assert t.dtype == torch.uint8 and t.is_cuda and t.is_contiguous() and tuple(t.shape) == (B, H, W_, 3)
     for t in (uv1, uv2):
         assert t.dtype == torch.float64 and t.is_cuda and t.is_contiguous() and tuple(t.shape) == (B, 21, 2)
     dev = img1.device
+    out = resize_size(out_size, (H, W_))
+    if out is not None:
+        Ho, Wo = out
+        s1, s2 = resize_joints(uv1, (H, W_), out), resize_joints(uv2, (H, W_), out)
+        xh1 = torch.empty((B, Ho, Wo, 4), dtype=torch.float32, device=dev)
+        xh2 = torch.empty((B, Ho, Wo, 4), dtype=torch.float32, device=dev)
+        xp = torch.empty((B, Ho, Wo, 44), dtype=torch.float32, device=dev)
+        xd = torch.empty((B, Ho, Wo, 8), dtype=torch.float32, device=dev)
+        L.call("mmh_decode_inputs_resized", _ptr(img1), _ptr(img2), _ptr(dep1), _ptr(dep2), _ptr(s1), _ptr(s2),
+               B, H, W_, Ho, Wo, float(sigma), _ptr(xh1), _ptr(xh2), _ptr(xp), _ptr(xd), _stream())
+        return xh1, xh2, xp, xd
     xh1 = torch.empty((B, H, W_, 4), dtype=torch.float32, device=dev)
     xh2 = torch.empty((B, H, W_, 4), dtype=torch.float32, device=dev)
     xp = torch.empty((B, H, W_, 44), dtype=torch.float32, device=dev)

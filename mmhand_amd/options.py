@@ -20,7 +20,10 @@ Differences, all deliberate:
   * three additions: --G_n_blocks (the reference hard-codes 9), --vgg_weights (file with
     torchvision vgg19.features[0:4] weights; there is no download path offline) and
     --vgg_random_init (explicit opt-in to seeded random VGG weights; without either of the two
-    the default --L1_type l1_plus_perL1 refuses to start).
+    the default --L1_type l1_plus_perL1 refuses to start);
+  * --resize_inputs N (addition; 0 = off): file-fed batches (--dataroot) reach the networks at N x N whatever size the
+    files hold - the resize happens inside the device's decode pass (ops.decode_inputs).  --fineSize keeps the dead
+    meaning it has in the reference (declared, never read).
 """
 import argparse
 import os
@@ -89,6 +92,10 @@ _BASE = [
                           help="with --dataroot: the loader uploads the PNG files' bytes and the device inflates and unfilters "
                                "them (mmh_png_decode_batch); files that are not 8-bit RGB non-interlaced go through PIL; "
                                "= MMH_DEVICE_PNG=1")),
+    ("--resize_inputs", dict(type=int, default=0,
+                             help="with --dataroot: feed the networks N x N images whatever size the files hold (0 = the "
+                                  "files' size); bilinear with half-pixel centres inside the device's decode pass, joints "
+                                  "scaled with it, sigma unchanged; N a multiple of 4")),
 ]
 _TRAIN = [
     ("--display_freq", dict(type=int, default=100)),
@@ -138,6 +145,15 @@ def check_exact_fwd(opt):
     return opt
 
 
+def check_resize_inputs(opt):
+    """--resize_inputs N: 0 = off, else the square target of the device's decode pass - a multiple of 4, as the networks'
+    two stride-2 stages need it.  Returns N."""
+    n = getattr(opt, "resize_inputs", 0) or 0
+    if isinstance(n, bool) or not isinstance(n, int) or n < 0 or n % 4 != 0:
+        raise ValueError(f"--resize_inputs {n!r}: expected 0 (off) or a positive multiple of 4")
+    return n
+
+
 class BaseOptions:
     isTrain = None
     _extra = []
@@ -159,6 +175,7 @@ class BaseOptions:
             check_exact_fwd(opt)
         except ValueError as e:
             self.parser.error(str(e))
+        check_resize_inputs(opt)        # a ValueError, as for a namespace built in code (MMHandModel checks those)
         opt.isTrain = self.isTrain
         import torch
         if opt.distributed:

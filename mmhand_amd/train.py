@@ -7,7 +7,9 @@ Same loop shape (epochs x batches, set_input + optimize_parameters, print/save c
 *samples*, update_learning_rate per epoch) and the same loss_log.txt line format
 (util/visualizer.py:116-123).  Data: with `--dataroot DIR --dataset rhd|stb` the reference's prepared directory
 (annotation.pickle + colour / depth PNGs; data.HandFolderLoader, decoded on the device), else synthetic RHD/STB-shaped
-batches (`--synthetic_samples N` sets the epoch length)."""
+batches (`--synthetic_samples N` sets the epoch length).  `--resize_inputs N` with `--dataroot`: the networks train at
+N x N whatever size the files hold - the raw batches travel at the files' size and the device's decode pass writes N x N
+(MMHandModel.set_input; synthetic batches keep `--fineSize`)."""
 import os
 import sys
 import time
