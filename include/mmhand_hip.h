@@ -915,6 +915,28 @@ enum {
 int mmh_png_decode_batch(const void* streams, int64_t streams_bytes, const int64_t* offsets, int N, int H, int W, void* scratch,
                          void* out, int32_t* status, int bgr, mmh_stream_t s);
 
+/* ---- PNG encode of a batch on the device (aug.py:66-71: one cv2.imwrite per generated image) ---------------------------------
+ * N images of H x W 8-bit pixels -> N zlib streams, each the whole IDAT payload of an 8-bit, colour type 2, non-interlaced
+ * PNG: every row filtered with the type (0 - 4) of the smallest sum of absolute values, then Huffman-only DEFLATE - one
+ * dynamic block of literals per 16 rows, no matches - and the Adler-32 trailer.  Two launches over (image, 16-row segment).
+ *   pixels     : device uint8 [N][H][W][3], B,G,R per pixel if bgr != 0, else R,G,B (the stream always holds R,G,B)
+ *   scratch    : device bytes, mmh_png_encode_scratch_bytes(N, H, W) of them, 16-byte aligned
+ *   streams    : device bytes, N slots of slot_bytes each; image i's stream is the first lengths[i] bytes of slot i, the rest
+ *                of the slot is left as it was
+ *   lengths    : device int64 [N]
+ *   status     : device int32 [N]: MMH_PNGENC_OK, or MMH_PNGENC_E_ROOM for an image whose stream is longer than slot_bytes:
+ *                its slot is left untouched, lengths[i] is the size it needs, the other images are not disturbed
+ * mmh_png_encode_slot_bytes(H, W) is a slot size no image can exceed (9 bits per filtered byte plus the block headers; it is
+ * derived in csrc/png_deflate.h), -1 for sizes the encoder rejects.  Host-side argument errors (N < 0, H or W < 1,
+ * H * (1 + 3 W) >= 2^31, slot_bytes < 8, a null pointer or a misaligned scratch with N > 0) return non-zero before any launch.
+ * The container (signature, IHDR, chunk CRCs) is the host's: mmhand_amd/png.py.                                              */
+enum { MMH_PNGENC_OK = 0, MMH_PNGENC_E_ROOM = 1 };
+int64_t mmh_png_encode_slot_bytes(int H, int W);          /* host only */
+int64_t mmh_png_encode_scratch_bytes(int N, int H, int W);
+int mmh_png_encode_batch(const void* pixels /* uint8 [N][H][W][3] */, int N, int H, int W, int bgr, void* scratch,
+                         void* streams /* N slots */, int64_t slot_bytes, int64_t* lengths /* [N] */, int32_t* status /* [N] */,
+                         mmh_stream_t s);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }

@@ -6,7 +6,12 @@ unfilters and writes uint8 [N,H,W,3] in cv2.imread's B,G,R order, the batch `mmh
 prepared RHD / STB directories hold goes to the device: 8-bit, colour type 2 (RGB), non-interlaced, all of one size.  Any
 other file (16-bit, palette, grey, alpha, Adam7, another size, a container error) and any image whose device status is not 0
 is decoded by PIL exactly as `data._read_bgr` does and copied into its slot; the caller is told which and why.  A file PIL
-rejects too raises, as it does on the default path."""
+rejects too raises, as it does on the default path.
+
+The other direction (opt-in: `python -m mmhand_amd.aug ... --device_png`): `PngBatchEncoder` hands a uint8 [N,H,W,3] device
+batch to `mmh_png_encode_batch` (csrc/png_encode.hip: row filters + Huffman-only DEFLATE, one zlib stream per image), fetches
+the streams and wraps each in the container (`write_png`: signature, IHDR, one IDAT, IEND, CRCs by zlib.crc32).  An image whose
+device status is not 0 is encoded by PIL from the same pixels and reported, as on the decode side."""
 import ctypes as C
 import io
 import struct
@@ -70,6 +75,27 @@ def pil_decode(data, bgr=True):
     with Image.open(io.BytesIO(data)) as im:
         rgb = np.asarray(im.convert("RGB"), dtype=np.uint8)
     return np.ascontiguousarray(rgb[:, :, ::-1]) if bgr else np.ascontiguousarray(rgb)
+
+
+def _chunk(typ, body):
+    return struct.pack(">I", len(body)) + typ + body + struct.pack(">I", zlib.crc32(body, zlib.crc32(typ)))
+
+
+def write_png(w, h, idat):
+    """the file around one zlib stream: signature, IHDR (8-bit, colour type 2, no interlace), one IDAT, IEND"""
+    return (SIGNATURE + _chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 2, 0, 0, 0)) + _chunk(b"IDAT", bytes(idat))
+            + _chunk(b"IEND", b""))
+
+
+def pil_encode(rgb):
+    """PIL's default PNG of uint8 [H,W,3] R,G,B pixels (what aug.py writes without --device_png)"""
+    from PIL import Image
+    b = io.BytesIO()
+    Image.fromarray(np.ascontiguousarray(rgb)).save(b, format="PNG")
+    return b.getvalue()
+
+
+ENC_STATUS = {0: "ok", 1: "stream longer than its slot"}
 
 
 def _pinned(n, dtype):
@@ -185,3 +211,96 @@ def decode_png_batch(files, device, bgr=True, stream=None):
     """files: the bytes of N PNG files of one size -> (uint8 [N,H,W,3] on `device`, B,G,R per pixel if bgr else R,G,B;
     [(index, reason)] for the files that went through PIL instead of the device)."""
     return PngBatchDecoder(device).decode(list(files), bgr=bgr, stream=stream)
+
+
+class PngBatchEncoder:
+    """One set of buffers - scratch / stream slots / lengths / status on the device, pinned lengths / status / streams on the
+    host - for batches of up to `capacity` images of one size; reused batch after batch (it grows only when a batch needs
+    more).  `launch` enqueues the encode and the copy of lengths and statuses and returns at once; `fetch` waits for them,
+    copies each stream's bytes (not the slots' slack) and builds the files - so a caller may enqueue other work in between.
+    One plan at a time: the buffers belong to the launched batch until it is fetched, and a second `launch` before raises.
+    slot_bytes: a smaller slot than mmh_png_encode_slot_bytes (tests; an image that does not fit goes through PIL)."""
+
+    def __init__(self, device, slot_bytes=None):
+        self.device = torch.empty(0, device=device).device          # "cuda" -> the current device, with its index
+        self.cap = self.shape = None
+        self.slot_override = slot_bytes
+        self.done = None
+        self.in_flight = False
+
+    def _reserve(self, n, h, w):
+        if self.cap is None or n > self.cap or (h, w) != self.shape:
+            lib = L.load()
+            self.cap, self.shape = n, (h, w)
+            self.slot = int(self.slot_override or lib.mmh_png_encode_slot_bytes(h, w))
+            if self.slot < 8:
+                raise ValueError(f"PNG batch: cannot encode images of {h}x{w}")
+            self.scratch = torch.empty(int(lib.mmh_png_encode_scratch_bytes(n, h, w)), dtype=torch.uint8, device=self.device)
+            self.slots_d = torch.empty((n, self.slot), dtype=torch.uint8, device=self.device)
+            self.len_d = torch.empty(n, dtype=torch.int64, device=self.device)
+            self.st_d = torch.empty(n, dtype=torch.int32, device=self.device)
+            self.len_h, self.st_h = _pinned(n, torch.int64), _pinned(n, torch.int32)
+            self.slots_h = _pinned(n * self.slot, torch.uint8).view(n, self.slot)
+
+    def launch(self, pixels, bgr=False, stream=None):
+        """device half: pixels uint8 [N,H,W,3] on the device (kept alive by the returned plan until `fetch`)"""
+        if pixels.dtype != torch.uint8 or pixels.dim() != 4 or pixels.shape[3] != 3 or pixels.device != self.device:
+            raise ValueError("PNG batch: expected a uint8 [N,H,W,3] tensor on the encoder's device")
+        pixels = pixels.contiguous()
+        n, h, w, _ = pixels.shape
+        if self.in_flight:
+            raise RuntimeError("PngBatchEncoder.launch: the previous batch has not been fetched; its buffers are still in use")
+        if n == 0:
+            return pixels, bool(bgr), None
+        if self.done is not None:
+            self.done.synchronize()             # the previous batch has left this set's buffers
+        self._reserve(n, h, w)
+        stream = stream or torch.cuda.current_stream(self.device)
+        with torch.cuda.stream(stream):
+            L.call("mmh_png_encode_batch", C.c_void_p(pixels.data_ptr()), n, h, w, int(bool(bgr)),
+                   C.c_void_p(self.scratch.data_ptr()), C.c_void_p(self.slots_d.data_ptr()), self.slot,
+                   C.c_void_p(self.len_d.data_ptr()), C.c_void_p(self.st_d.data_ptr()), C.c_void_p(stream.cuda_stream))
+            self.len_h[:n].copy_(self.len_d[:n], non_blocking=True)
+            self.st_h[:n].copy_(self.st_d[:n], non_blocking=True)
+            self.done = torch.cuda.Event()
+            self.done.record(stream)
+        self.in_flight = True
+        return pixels, bool(bgr), stream
+
+    def fetch(self, plan):
+        """host half -> (list of N files' bytes, [(index, reason)] for the images PIL encoded instead)"""
+        pixels, bgr, stream = plan
+        n, h, w, _ = pixels.shape
+        if n == 0:
+            return [], []
+        if not self.in_flight:
+            raise RuntimeError("PngBatchEncoder.fetch: no launched batch to fetch")
+        self.done.synchronize()
+        lengths, status = self.len_h[:n].numpy().copy(), self.st_h[:n].numpy().copy()
+        with torch.cuda.stream(stream):
+            for i in range(n):
+                if status[i] == 0:
+                    k = int(lengths[i])
+                    self.slots_h[i, :k].copy_(self.slots_d[i, :k], non_blocking=True)
+            self.done = torch.cuda.Event()
+            self.done.record(stream)
+        self.done.synchronize()
+        self.in_flight = False
+        files, report = [], []
+        for i in range(n):
+            if status[i] == 0:
+                files.append(write_png(w, h, self.slots_h[i, :int(lengths[i])].numpy().tobytes()))
+                continue
+            report.append((i, f"device status {int(status[i])}: {ENC_STATUS.get(int(status[i]), '?')}"))
+            px = pixels[i].cpu().numpy()
+            files.append(pil_encode(px[:, :, ::-1] if bgr else px))
+        return files, report
+
+    def encode(self, pixels, bgr=False, stream=None):
+        return self.fetch(self.launch(pixels, bgr=bgr, stream=stream))
+
+
+def encode_png_batch(pixels, bgr=False, stream=None):
+    """pixels: uint8 [N,H,W,3] on a device, B,G,R per pixel if bgr else R,G,B -> (the bytes of N PNG files, [(index, reason)]
+    for the images that went through PIL instead of the device)"""
+    return PngBatchEncoder(pixels.device).encode(pixels, bgr=bgr, stream=stream)
