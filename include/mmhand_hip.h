@@ -836,6 +836,33 @@ int mmh_decode_inputs_resized(const void* img1, const void* img2, const void* de
                               int B, int Hs, int Ws, int Ho, int Wo, double sigma,
                               void* x_h1, void* x_h2, void* x_p, void* x_d, mmh_stream_t s);
 
+/* ---- resident dataset: the decoded images stay in device memory, batches are named by slot ----
+ * replaces the loop of data/mmhand_dataset_data_loader.py:22-48 over data/generic_dataset.py:133-180
+ * that re-reads and re-decodes every file every epoch (fixed order, no shuffle, a sampler whose
+ * epoch never advances: every epoch asks for the same files).
+ * mmh_store_images scatters a decoded batch into the store:
+ *   src    uint8 [N,H,W,3]
+ *   slots  device int32 [N]: image n goes to store[slots[n]]; -1 = skip this image
+ *   store  uint8 [S,H,W,3]
+ *   status device int32 [1] or NULL: a slot outside [-1, S) writes nothing and ORs 1 into it */
+int mmh_store_images(const void* src, const void* slots, int N, int H, int W,
+                     void* store, int64_t S, void* status, mmh_stream_t s);
+/* mmh_decode_inputs / mmh_decode_inputs_resized reading their sources out of a resident store
+ * instead of a batch (data/generic_dataset.py:133-180 without its cv2.imread calls, and with
+ * data/mmhand_dataset_data_loader.py:22-48's collation reduced to a row of slots):
+ *   store    uint8 [S,Hs,Ws,3] BGR
+ *   idx      device int32 [B,4] = slots of (img1, img2, dep1, dep2) of each sample
+ *   uv_table float64 [S,21,2], joints ALREADY on the Ho x Wo grid; sample b takes rows
+ *            idx[b][0] and idx[b][1]
+ * Outputs and arithmetic are exactly those two entry points' (Ho x Wo == Hs x Ws is the plain
+ * pass); the outputs must be 16-byte aligned.  A sample with a slot outside [0, S) is written as
+ * zeros (all of its lanes) and ORs 1 into *status (device int32 [1], may be NULL); every byte
+ * offset into the store is 64-bit.                                                          */
+int mmh_decode_inputs_indexed(const void* store, int64_t S, int Hs, int Ws, const void* idx,
+                              const void* uv_table, int B, int Ho, int Wo, double sigma,
+                              void* x_h1, void* x_h2, void* x_p, void* x_d, void* status,
+                              mmh_stream_t s);
+
 /* ---- data-parallel gradient all-reduce (apex DistributedDataParallel behind
  * models/MMHandModel.py:109-116; reduce_tensor :381-384) -------------------------
  * The training process already holds ONE RCCL communicator per GPU (torch.distributed's "nccl"

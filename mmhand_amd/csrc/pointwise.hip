@@ -1975,6 +1975,52 @@ __device__ __forceinline__ double depth_raw(const uint8_t* p) { return 256.0 * (
 __device__ __forceinline__ float depth_f64(double d) { return (float)(((d / 700.0) - 0.5) / 0.5); }
 
 constexpr int DECODE_LANES = 15;
+// Lane q (one float4) of output pixel px = (x, y) of ONE sample: q = 0, 1 -> x_h1, x_h2; 2, 3 -> x_d; 4 .. 14 -> x_p.  img1 .. dep2
+// point at that sample's Hs x Ws sources and u1, u2 at its joints, wherever they live (a batch, or slots of a resident
+// store); px indexes the OUTPUT batch.  The per-pixel arithmetic of the resized and the indexed pass, in one place.
+__device__ __forceinline__ void decode_lane(const uint8_t* __restrict__ img1, const uint8_t* __restrict__ img2,
+                                            const uint8_t* __restrict__ dep1, const uint8_t* __restrict__ dep2,
+                                            const double* __restrict__ u1, const double* __restrict__ u2,
+                                            int q, int64_t px, int x, int y, int Hs, int Ws, int Ho, int Wo, double sigma,
+                                            float* __restrict__ xh1, float* __restrict__ xh2,
+                                            float* __restrict__ xp, float* __restrict__ xd) {
+    if (q >= 4) {
+        // pose maps: channels 4 (q - 4) .. + 3 of 44 (P1 in 0..20, P2 in 21..41, 42 and 43 zero)
+        float v[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int c = (q - 4) * 4 + e;
+            v[e] = c < 21 ? heat((double)x, (double)y, u1[2 * c], u1[2 * c + 1], sigma)
+                 : c < 42 ? heat((double)x, (double)y, u2[2 * (c - 21)], u2[2 * (c - 21) + 1], sigma) : 0.f;
+        }
+        st4(xp, px * 11 + (q - 4), make_float4(v[0], v[1], v[2], v[3]));
+        return;
+    }
+    const ResizeTap tx = resize_tap(x, Ws, Wo), ty = resize_tap(y, Hs, Ho);
+    const int64_t row0 = (int64_t)ty.i0 * Ws, row1 = (int64_t)ty.i1 * Ws;
+    const int64_t o00 = (row0 + tx.i0) * 3, o01 = (row0 + tx.i1) * 3, o10 = (row1 + tx.i0) * 3, o11 = (row1 + tx.i1) * 3;
+    if (q < 2) {
+        // images: BGR uint8 -> RGB normalised
+        const uint8_t* p = q == 0 ? img1 : img2;
+        float c[3];
+#pragma unroll
+        for (int e = 0; e < 3; ++e)
+            c[e] = norm_f64(lerp2((double)p[o00 + e], (double)p[o01 + e], (double)p[o10 + e], (double)p[o11 + e], tx.w, ty.w));
+        st4(q == 0 ? xh1 : xh2, px, make_float4(c[2], c[1], c[0], 0.f));
+    } else {
+        // depth: 256*G + R per tap (BGR order: index 1 = G, 2 = R), interpolated, then / 700 and normalised
+        const float d2 = depth_f64(lerp2(depth_raw(dep2 + o00), depth_raw(dep2 + o01), depth_raw(dep2 + o10),
+                                         depth_raw(dep2 + o11), tx.w, ty.w));
+        if (q == 2) {
+            const float d1 = depth_f64(lerp2(depth_raw(dep1 + o00), depth_raw(dep1 + o01), depth_raw(dep1 + o10),
+                                             depth_raw(dep1 + o11), tx.w, ty.w));
+            st4(xd, px * 2, make_float4(d1, d1, d1, d2));
+        } else {
+            st4(xd, px * 2 + 1, make_float4(d2, d2, 0.f, 0.f));
+        }
+    }
+}
+
 __global__ void decode_inputs_resized_kernel(const uint8_t* __restrict__ img1, const uint8_t* __restrict__ img2,
                                              const uint8_t* __restrict__ dep1, const uint8_t* __restrict__ dep2,
                                              const double* __restrict__ uv1, const double* __restrict__ uv2,
@@ -1982,6 +2028,7 @@ __global__ void decode_inputs_resized_kernel(const uint8_t* __restrict__ img1, c
                                              float* __restrict__ xh1, float* __restrict__ xh2,
                                              float* __restrict__ xp, float* __restrict__ xd) {
     const int64_t total = (int64_t)B * Ho * Wo * DECODE_LANES;
+    const int64_t img_bytes = (int64_t)Hs * Ws * 3;
     int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (; i < total; i += stride) {
@@ -1990,44 +2037,66 @@ __global__ void decode_inputs_resized_kernel(const uint8_t* __restrict__ img1, c
         const int x = (int)(px % Wo);
         const int64_t t = px / Wo;
         const int y = (int)(t % Ho);
-        const int b = (int)(t / Ho);
-        if (q >= 4) {
-            // pose maps: channels 4 (q - 4) .. + 3 of 44 (P1 in 0..20, P2 in 21..41, 42 and 43 zero)
-            const double* u1 = uv1 + (int64_t)b * 42;
-            const double* u2 = uv2 + (int64_t)b * 42;
-            float v[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int c = (q - 4) * 4 + e;
-                v[e] = c < 21 ? heat((double)x, (double)y, u1[2 * c], u1[2 * c + 1], sigma)
-                     : c < 42 ? heat((double)x, (double)y, u2[2 * (c - 21)], u2[2 * (c - 21) + 1], sigma) : 0.f;
-            }
-            st4(xp, px * 11 + (q - 4), make_float4(v[0], v[1], v[2], v[3]));
+        const int64_t b = t / Ho;
+        decode_lane(img1 + b * img_bytes, img2 + b * img_bytes, dep1 + b * img_bytes, dep2 + b * img_bytes, uv1 + b * 42,
+                    uv2 + b * 42, q, px, x, y, Hs, Ws, Ho, Wo, sigma, xh1, xh2, xp, xd);
+    }
+}
+
+// ------------------------------------------------------------------ resident dataset
+// The decoded dataset stays in device memory as uint8 [S,Hs,Ws,3]; a batch is a row of slots.  Slots come from a table, so
+// both kernels guard them with plain branches: a bad row costs its sample (zeros / nothing written) and a status bit, never
+// a fault.  Every offset into the store is 64-bit (slot * Hs * Ws * 3 passes 2^31 at slot 10,923 of a 256 x 256 store).
+//
+// T = uint4 (images of a multiple of 16 bytes in 16-byte aligned buffers) or uint8_t; per = words of one image
+template <typename T>
+__global__ void store_images_kernel(const T* __restrict__ src, const int* __restrict__ slots, int N, int64_t per,
+                                    T* __restrict__ store, int64_t S, int* __restrict__ status) {
+    const int64_t total = (int64_t)N * per;
+    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (; i < total; i += stride) {
+        const int64_t r = i % per;
+        const int64_t slot = slots[i / per];
+        if (slot == -1) continue;                       // already resident
+        if (slot < -1 || slot >= S) {
+            if (status && r == 0) atomicOr(status, 1);
             continue;
         }
-        const ResizeTap tx = resize_tap(x, Ws, Wo), ty = resize_tap(y, Hs, Ho);
-        const int64_t row0 = ((int64_t)b * Hs + ty.i0) * Ws, row1 = ((int64_t)b * Hs + ty.i1) * Ws;
-        const int64_t o00 = (row0 + tx.i0) * 3, o01 = (row0 + tx.i1) * 3, o10 = (row1 + tx.i0) * 3, o11 = (row1 + tx.i1) * 3;
-        if (q < 2) {
-            // images: BGR uint8 -> RGB normalised
-            const uint8_t* p = q == 0 ? img1 : img2;
-            float c[3];
-#pragma unroll
-            for (int e = 0; e < 3; ++e)
-                c[e] = norm_f64(lerp2((double)p[o00 + e], (double)p[o01 + e], (double)p[o10 + e], (double)p[o11 + e], tx.w, ty.w));
-            st4(q == 0 ? xh1 : xh2, px, make_float4(c[2], c[1], c[0], 0.f));
-        } else {
-            // depth: 256*G + R per tap (BGR order: index 1 = G, 2 = R), interpolated, then / 700 and normalised
-            const float d2 = depth_f64(lerp2(depth_raw(dep2 + o00), depth_raw(dep2 + o01), depth_raw(dep2 + o10),
-                                             depth_raw(dep2 + o11), tx.w, ty.w));
-            if (q == 2) {
-                const float d1 = depth_f64(lerp2(depth_raw(dep1 + o00), depth_raw(dep1 + o01), depth_raw(dep1 + o10),
-                                                 depth_raw(dep1 + o11), tx.w, ty.w));
-                st4(xd, px * 2, make_float4(d1, d1, d1, d2));
-            } else {
-                st4(xd, px * 2 + 1, make_float4(d2, d2, 0.f, 0.f));
-            }
+        store[slot * per + r] = src[i];
+    }
+}
+
+// decode_inputs_resized_kernel with each sample's four sources and two joint rows looked up by slot.  The lane layout (15
+// float4 per output pixel, a wave's stores into x_p contiguous) is that kernel's; Ho x Wo == Hs x Ws makes every tap weight
+// 0 and the result the plain pass's, bit for bit.
+__global__ void decode_inputs_indexed_kernel(const uint8_t* __restrict__ store, int64_t S, int Hs, int Ws,
+                                             const int* __restrict__ idx, const double* __restrict__ uvt,
+                                             int B, int Ho, int Wo, double sigma,
+                                             float* __restrict__ xh1, float* __restrict__ xh2,
+                                             float* __restrict__ xp, float* __restrict__ xd, int* __restrict__ status) {
+    const int64_t total = (int64_t)B * Ho * Wo * DECODE_LANES;
+    const int64_t img_bytes = (int64_t)Hs * Ws * 3;
+    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (; i < total; i += stride) {
+        const int q = (int)(i % DECODE_LANES);
+        const int64_t px = i / DECODE_LANES;
+        const int x = (int)(px % Wo);
+        const int64_t t = px / Wo;
+        const int y = (int)(t % Ho);
+        const int64_t b = t / Ho;
+        const int64_t s0 = idx[b * 4], s1 = idx[b * 4 + 1], s2 = idx[b * 4 + 2], s3 = idx[b * 4 + 3];
+        if (s0 < 0 || s0 >= S || s1 < 0 || s1 >= S || s2 < 0 || s2 >= S || s3 < 0 || s3 >= S) {
+            const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (q >= 4) st4(xp, px * 11 + (q - 4), z);
+            else if (q >= 2) st4(xd, px * 2 + (q - 2), z);
+            else st4(q == 0 ? xh1 : xh2, px, z);
+            if (status && q == 0 && x == 0 && y == 0) atomicOr(status, 1);
+            continue;
         }
+        decode_lane(store + s0 * img_bytes, store + s1 * img_bytes, store + s2 * img_bytes, store + s3 * img_bytes,
+                    uvt + s0 * 42, uvt + s1 * 42, q, px, x, y, Hs, Ws, Ho, Wo, sigma, xh1, xh2, xp, xd);
     }
 }
 
@@ -3015,6 +3084,39 @@ int mmh_decode_inputs_resized(const void* img1, const void* img2, const void* de
                        static_cast<const double*>(uv2), B, Hs, Ws, Ho, Wo, sigma, static_cast<float*>(x_h1),
                        static_cast<float*>(x_h2), static_cast<float*>(x_p), static_cast<float*>(x_d));
     return mmh::check_launch("decode_inputs_resized");
+}
+
+int mmh_store_images(const void* src, const void* slots, int N, int H, int W, void* store, int64_t S, void* status,
+                     mmh_stream_t s) {
+    MMH_REQUIRE(src && slots && store, "mmh_store_images: NULL buffer");
+    MMH_REQUIRE(N > 0 && H > 0 && W > 0, "mmh_store_images: bad shape");
+    MMH_REQUIRE(S >= 1, "mmh_store_images: S must be at least 1");
+    const int64_t bytes = (int64_t)H * W * 3;
+    if (bytes % 16 == 0 && ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(store)) & 15) == 0)
+        hipLaunchKernelGGL(store_images_kernel<uint4>, dim3(grid_for(N * (bytes / 16))), dim3(TPB), 0, mmh::as_stream(s),
+                           static_cast<const uint4*>(src), static_cast<const int*>(slots), N, bytes / 16,
+                           static_cast<uint4*>(store), S, static_cast<int*>(status));
+    else
+        hipLaunchKernelGGL(store_images_kernel<uint8_t>, dim3(grid_for(N * bytes)), dim3(TPB), 0, mmh::as_stream(s),
+                           static_cast<const uint8_t*>(src), static_cast<const int*>(slots), N, bytes,
+                           static_cast<uint8_t*>(store), S, static_cast<int*>(status));
+    return mmh::check_launch("store_images");
+}
+
+int mmh_decode_inputs_indexed(const void* store, int64_t S, int Hs, int Ws, const void* idx, const void* uv_table, int B,
+                              int Ho, int Wo, double sigma, void* x_h1, void* x_h2, void* x_p, void* x_d, void* status,
+                              mmh_stream_t s) {
+    MMH_REQUIRE(store && idx && uv_table && x_h1 && x_h2 && x_p && x_d, "mmh_decode_inputs_indexed: NULL buffer");
+    MMH_REQUIRE(B > 0 && Hs > 0 && Ws > 0 && Ho > 0 && Wo > 0 && sigma > 0, "mmh_decode_inputs_indexed: bad shape");
+    MMH_REQUIRE(S >= 1, "mmh_decode_inputs_indexed: S must be at least 1");
+    MMH_REQUIRE(((reinterpret_cast<uintptr_t>(x_h1) | reinterpret_cast<uintptr_t>(x_h2) | reinterpret_cast<uintptr_t>(x_p) |
+                  reinterpret_cast<uintptr_t>(x_d)) & 15) == 0, "mmh_decode_inputs_indexed: outputs must be 16-byte aligned");
+    hipLaunchKernelGGL(decode_inputs_indexed_kernel, dim3(grid_for((int64_t)B * Ho * Wo * DECODE_LANES)), dim3(TPB), 0,
+                       mmh::as_stream(s), static_cast<const uint8_t*>(store), S, Hs, Ws, static_cast<const int*>(idx),
+                       static_cast<const double*>(uv_table), B, Ho, Wo, sigma, static_cast<float*>(x_h1),
+                       static_cast<float*>(x_h2), static_cast<float*>(x_p), static_cast<float*>(x_d),
+                       static_cast<int*>(status));
+    return mmh::check_launch("decode_inputs_indexed");
 }
 
 int mmh_prep_weights_bf16(const void* w, int taps, int Cin, int Cout, void* w_plain, void* w_t,

@@ -16,7 +16,12 @@ data/mmhand_dataset.py (CSV pairs + .npy pose arrays) is not read.
 
 `HandFolderLoader(device_png=True)` (--device_png, MMH_DEVICE_PNG=1; off by default) moves the boundary from decoded pixels
 to the files' bytes: the threads only read the files, the batch's zlib streams go up as one pinned buffer and
-mmh_png_decode_batch (png.py) writes the same uint8 [B,H,W,3] BGR tensors."""
+mmh_png_decode_batch (png.py) writes the same uint8 [B,H,W,3] BGR tensors.
+
+`HandFolderLoader(resident=True)` (--resident_dataset, MMH_RESIDENT_DATASET=1; off by default): the loader's order never
+changes between epochs, so the decoded images of this rank's batches are kept in device memory (uint8 [S,Hs,Ws,3], one slot
+per file).  The first epoch reads the files as above and copies each batch into the store (mmh_store_images); from then on a
+batch is a row of slots and ONE kernel (mmh_decode_inputs_indexed) - no file read, no PNG decode, no upload."""
 import os
 import pickle
 import random
@@ -89,6 +94,95 @@ def _read_bytes(path):
 _IMAGE_KEYS = ("img1", "img2", "dep1", "dep2")
 
 
+# ----------------------------------------------------------------------------- resident dataset: host-side planning
+def _batch_groups(indices, batch_size, max_batches):
+    """the loader's batches as lists of pair indices: in order, the last one may be short, at most `max_batches` of them (the
+    reference compares the BATCH index with max_dataset_size)"""
+    groups = [list(indices[i:i + batch_size]) for i in range(0, len(indices), batch_size)]
+    return groups[: int(min(len(groups), max_batches))]
+
+
+def resident_plan(image_source, image_target, indices, batch_size, max_batches=float("inf")):
+    """Which files one rank's batches touch, and where each batch finds them: pure host code, no torch.
+
+    -> (paths, table).  paths: the unique files in order of first use - every colour file and its "color" -> "depth" twin;
+    a file that is source in one pair and target in another has ONE slot.  table: int32 [n_batches, batch_size, 4] = the
+    slots of (img1, img2, dep1, dep2) of every sample.  A short last batch keeps its own length: its unused rows are -1 and
+    are never handed to the device (`table_lengths`), they are not padding a kernel reads."""
+    groups = _batch_groups(indices, batch_size, max_batches)
+    slot, paths = {}, []
+
+    def slot_of(path):
+        if path not in slot:
+            slot[path] = len(paths)
+            paths.append(path)
+        return slot[path]
+
+    table = np.full((len(groups), int(batch_size), 4), -1, dtype=np.int32)
+    for g, items in enumerate(groups):
+        for r, item in enumerate(items):
+            h1, h2 = image_source[item], image_target[item]
+            table[g, r] = [slot_of(h1), slot_of(h2), slot_of(h1.replace("color", "depth")), slot_of(h2.replace("color", "depth"))]
+    return paths, table
+
+
+def table_lengths(table):
+    """samples per batch of a resident_plan table (the rows in front of the first unused one)"""
+    return [int((t[:, 0] >= 0).sum()) for t in table]
+
+
+def check_table(table, n_slots):
+    """The host's range check of a batch table, before it is uploaded: every used row names four slots in [0, n_slots), the
+    unused rows (all -1) come last in their batch.  The kernels guard their slots too, but a table that fails here is a bug
+    of the plan, and says so."""
+    table = np.asarray(table)
+    if table.dtype != np.int32 or table.ndim != 3 or table.shape[2] != 4:
+        raise ValueError(f"batch table: expected int32 [n_batches, B, 4], got {table.dtype} {table.shape}")
+    for g, t in enumerate(table):
+        n = int((t[:, 0] >= 0).sum())
+        if n == 0 or (t[n:] != -1).any():
+            raise ValueError(f"batch table: batch {g} is empty or has rows after its unused ones")
+        if (t[:n] < 0).any() or (t[:n] >= n_slots).any():
+            raise ValueError(f"batch table: batch {g} names a slot outside [0, {n_slots})")
+    return table
+
+
+def resident_decision(n_paths, Hs, Ws, budget_bytes, free_bytes=None):
+    """-> (bytes of the store, "on" | "off: <reason>").  All or nothing: a store that does not fit the budget (--resident_gb)
+    or the device's free memory is not built at all."""
+    need = int(n_paths) * int(Hs) * int(Ws) * 3
+    if n_paths < 1:
+        return need, "off: no files to hold"
+    if need > budget_bytes:
+        return need, f"off: {n_paths} images of {Hs} x {Ws} need {need} bytes, over the budget of {int(budget_bytes)} (--resident_gb)"
+    if free_bytes is not None and need > free_bytes:
+        return need, f"off: {n_paths} images of {Hs} x {Ws} need {need} bytes, the device has {int(free_bytes)} free"
+    return need, "on"
+
+
+def png_size(path):
+    """(height, width) out of a PNG file's IHDR, None for anything else"""
+    with open(path, "rb") as fh:
+        head = fh.read(24)
+    if len(head) < 24 or head[:8] != b"\x89PNG\r\n\x1a\n" or head[12:16] != b"IHDR":
+        return None
+    return int.from_bytes(head[20:24], "big"), int.from_bytes(head[16:20], "big")
+
+
+class ResidentBatch:
+    """One batch of a resident store: `idx` int32 [B,4] (a row block of the loader's device table) names the slots of
+    (img1, img2, dep1, dep2) in `store` uint8 [S,Hs,Ws,3]; `uv_table` float64 [S,21,2] holds every slot's joints on the grid
+    of `out_size` (the loader's --resize_inputs; None = the store's size).  ops.decode_inputs_indexed consumes it as it is."""
+
+    def __init__(self, store, idx, uv_table, out_size=None):
+        self.store, self.idx, self.uv_table, self.out_size = store, idx, uv_table, out_size
+        self.B = int(idx.shape[0])
+
+    def gather(self):
+        """the four uint8 [B,Hs,Ws,3] tensors a raw batch carries (img1, img2, dep1, dep2), copied out of the store"""
+        return tuple(self.store[self.idx[:, j].long()] for j in range(4))
+
+
 class HandFolderLoader:
     """Iterable of RAW device batches over a prepared RHD / STB directory; `MMHandModel.set_input` decodes them on the
     device (keys img1, img2, dep1, dep2: uint8 [B,H,W,3] BGR as cv2.imread delivers them; uv1, uv2: float64 [B,21,2];
@@ -109,7 +203,7 @@ class HandFolderLoader:
         world size, rank r takes r, r + world, ...); the last batch may be short; iteration stops after
         `max_dataset_size` BATCHES (the reference compares the batch index with it)."""
 
-    def __init__(self, opt, device=None, decoded=False, threads=None, device_png=None):
+    def __init__(self, opt, device=None, decoded=False, threads=None, device_png=None, resident=None):
         self.opt = opt
         # --resize_inputs N: the decoded form (decoded=True) comes out at N x N (joints in C1 / C2 scaled with it); the raw
         # form always travels at the files' size - MMHandModel.set_input resizes inside its decode pass
@@ -156,6 +250,13 @@ class HandFolderLoader:
         self.png_fallbacks = []
         self._png_sets = self._png_stream = self._png_prev = None
         self._png_turn = 0
+        # opt-in: the decoded dataset stays on the device (see the module docstring); "off: <reason>" = asked for and refused
+        if resident is None:
+            resident = bool(getattr(opt, "resident_dataset", False)) or os.environ.get("MMH_RESIDENT_DATASET", "0") == "1"
+        self.resident_state = "off"
+        self._res = None
+        if resident:
+            self._resident_setup()
 
     def _get_src_tgt(self, ratio, data, sort_fn):
         assert len(data) > 0, "no images listed in annotation.pickle for this --dataset"
@@ -230,12 +331,13 @@ class HandFolderLoader:
         out["H2_path"] = [s["H2_path"] for s in samples]
         return out
 
-    def host_batches(self):
-        """pinned host batches in loader order, file reads on a thread pool, one batch prepared ahead"""
+    def host_batches(self, only=None):
+        """pinned host batches in loader order, file reads on a thread pool, one batch prepared ahead; `only`: the numbers of
+        the batches to prepare (the resident loader's batches that still need their files), all of them when None"""
         from concurrent.futures import ThreadPoolExecutor
-        idx, B = self.indices(), self.opt.batchSize
-        groups = [idx[i:i + B] for i in range(0, len(idx), B)]
-        groups = groups[: int(min(len(groups), self.opt.max_dataset_size))]
+        groups = _batch_groups(self.indices(), self.opt.batchSize, self.opt.max_dataset_size)
+        if only is not None:
+            groups = [groups[g] for g in only]
         if not groups:
             return
         with ThreadPoolExecutor(max_workers=max(1, self.threads)) as pool:
@@ -265,10 +367,12 @@ class HandFolderLoader:
             self.png_fallbacks.append((path.replace("color", "depth") if i // B >= 2 else path, reason))
         return {k: pix[j * B:(j + 1) * B] for j, k in enumerate(_IMAGE_KEYS)}
 
-    def to_device(self, hb):
+    def to_device(self, hb, fill=None):
         out = {k: (v.to(self.device, non_blocking=True) if torch.is_tensor(v) else v) for k, v in hb.items() if k != "_png"}
         if "_png" in hb:
             out = {**self._png_to_device(hb), **out}
+        if fill is not None:
+            self._fill(fill, out)
         if not self.decoded:
             return out
         src = tuple(out["img1"].shape[1:3])
@@ -280,9 +384,99 @@ class HandFolderLoader:
         return {"H1": v(xh1, 3), "H2": v(xh2, 3), "P1": v(xp)[:, :21], "P2": v(xp)[:, 21:42], "D1": v(xd)[:, :3],
                 "D2": v(xd)[:, 3:6], "C1": c1, "C2": c2, "H1_path": out["H1_path"], "H2_path": out["H2_path"]}
 
+    # ------------------------------------------------------------------ resident dataset
+    def _resident_setup(self):
+        """plan, budget decision, store and tables; leaves `resident_state` "on" or "off: <reason>" (then nothing else differs
+        from a loader without the flag)"""
+        paths, table = resident_plan(self.image_source, self.image_target, self.indices(), self.opt.batchSize,
+                                     self.opt.max_dataset_size)
+        size = png_size(paths[0]) if paths else None
+        if size is None:
+            state = "off: no batches" if not paths else f"off: {paths[0]} is not a PNG file"
+        else:
+            free = torch.cuda.mem_get_info(self.device)[0]
+            budget = int(float(getattr(self.opt, "resident_gb", 64.0)) * 1e9)
+            need, state = resident_decision(len(paths), size[0], size[1], budget, free)
+        self.resident_state = state
+        if state != "on":
+            print(f"{self.name}: --resident_dataset {state}; batches keep coming from the files")
+            return
+        check_table(table, len(paths))
+        Hs, Ws = size
+        S, dev = len(paths), self.device
+        uv, c = np.zeros((S, 21, 2), np.float64), np.zeros((S, 21, 3), np.float64)
+        colour = set(self.image_source) | set(self.image_target)
+        for slot, path in enumerate(paths):
+            if path in colour:                          # the depth twins' rows are never read
+                a = self.get_labels(path)
+                uv[slot] = np.asarray(a["uv_coord"], dtype=np.float64).reshape(21, 2)
+                c[slot] = np.concatenate([uv[slot], np.expand_dims(np.asarray(a["depth"], dtype=np.float64), -1) / 700.0 * 255], -1)
+        uv, c = torch.from_numpy(uv).to(dev), torch.from_numpy(c).to(dev)
+        dst = ops.resize_size(self.out_size, size)
+        if dst is not None:                             # joints are scaled in ONE place, once
+            uv, c = ops.resize_joints(uv, size, dst), ops.resize_joints(c, size, dst)
+        self._res = dict(paths=paths, table=table, lengths=table_lengths(table), filled=np.zeros(S, dtype=bool), size=size,
+                         store=torch.empty((S, Hs, Ws, 3), dtype=torch.uint8, device=dev), uv=uv.contiguous(),
+                         c=c.contiguous(), table_dev=torch.from_numpy(table).to(dev))
+        self.resident_state = f"on: {S} images of {Hs} x {Ws}, {need} bytes"
+
+    def _batch_is_resident(self, g):
+        r = self._res
+        return bool(r["filled"][r["table"][g, : r["lengths"][g]]].all())
+
+    def _fill(self, g, out):
+        """copy a batch that came from the files into the store, on the current stream - behind the batch's upload (or the
+        wait for the PNG stream) and in front of whatever reads the store later on this stream.  Images already resident, and
+        a file's second appearance in the batch, get slot -1; images of another size than the store's never enter it."""
+        r = self._res
+        n = r["lengths"][g]
+        if tuple(out["img1"].shape) != (n,) + r["size"] + (3,):
+            return
+        slots = r["table"][g, :n].T.copy()              # [4, n]: one row per image key
+        fresh = ~r["filled"][slots]
+        _, first = np.unique(slots.ravel(), return_index=True)
+        once = np.zeros(slots.size, dtype=bool)
+        once[first] = True
+        fresh &= once.reshape(slots.shape)
+        if not fresh.any():
+            return
+        dev_slots = torch.from_numpy(np.where(fresh, slots, -1).astype(np.int32)).to(self.device)
+        for j, k in enumerate(_IMAGE_KEYS):
+            if fresh[j].any():
+                ops.store_images(out[k].contiguous(), dev_slots[j], r["store"])
+        r["filled"][slots[fresh]] = True
+
+    def _serve(self, g):
+        """batch g out of the store: no host work beyond this dictionary"""
+        r = self._res
+        n = r["lengths"][g]
+        idx = r["table_dev"][g, :n]
+        c1, c2 = r["c"][idx[:, 0].long()], r["c"][idx[:, 1].long()]
+        p1, p2 = ([r["paths"][s] for s in r["table"][g, :n, j]] for j in (0, 1))
+        rb = ResidentBatch(r["store"], idx, r["uv"], self.out_size)
+        if not self.decoded:
+            return {"resident": rb, "C1": c1, "C2": c2, "H1_path": p1, "H2_path": p2}
+        xh1, xh2, xp, xd = ops.decode_inputs_indexed(rb.store, rb.idx, rb.uv_table, out_size=rb.out_size)
+        v = ops.nhwc_to_nchw_view
+        return {"H1": v(xh1, 3), "H2": v(xh2, 3), "P1": v(xp)[:, :21], "P2": v(xp)[:, 21:42], "D1": v(xd)[:, :3],
+                "D2": v(xd)[:, 3:6], "C1": c1, "C2": c2, "H1_path": p1, "H2_path": p2}
+
     def __iter__(self):
-        for hb in self.host_batches():
-            yield self.to_device(hb)
+        if self._res is None:
+            for hb in self.host_batches():
+                yield self.to_device(hb)
+            return
+        # decided once per epoch: the batches whose slots are all filled come out of the store, the others take the file
+        # path unchanged and fill it on their way
+        n_batches = len(self._res["lengths"])
+        todo = [g for g in range(n_batches) if not self._batch_is_resident(g)]
+        from_files = self.host_batches(only=todo)
+        todo = set(todo)
+        try:
+            for g in range(n_batches):
+                yield self.to_device(next(from_files), fill=g) if g in todo else self._serve(g)
+        finally:
+            from_files.close()              # the thread pool goes with its last batch, not with the garbage collector
 
 
 def make_loader(opt, synthetic_samples=256, device=None):

@@ -545,6 +545,17 @@ class MMHandModel(torch.nn.Module):
                                                 ops.resize_joints(input[k].to(dev, non_blocking=True), src, dst)
                                                 for k in ("C1", "C2"))
             return self.set_input_raw(*[t[k] for k in raw], paths=(input["H1_path"], input["H2_path"]) if "H1_path" in input else None)
+        if "resident" in input:
+            # a batch of data.HandFolderLoader(resident=True) whose images already sit in the device's store: ONE kernel
+            # (mmh_decode_inputs_indexed) reads them by slot - no file, no PNG decode, no upload.  The tables are on the
+            # output grid of the loader's --resize_inputs, which is this model's (both read the same option)
+            rb = input["resident"]
+            assert (rb.out_size or 0) == (self.resize_inputs or 0), \
+                f"resident batch prepared for --resize_inputs {rb.out_size or 0}, the model runs {self.resize_inputs or 0}"
+            if "C1" in input and "C2" in input:
+                self.input_C1, self.input_C2 = input["C1"], input["C2"]
+            return self._set_decoded(lambda: ops.decode_inputs_indexed(rb.store, rb.idx, rb.uv_table, out_size=rb.out_size),
+                                     paths=(input["H1_path"], input["H2_path"]) if "H1_path" in input else None)
         keys = ("H1", "P1", "D1", "H2", "P2", "D2")
         if dev.type == "cuda" and any(not input[k].is_cuda for k in keys):
             if getattr(self, "_copy_stream", None) is None:
@@ -606,8 +617,13 @@ class MMHandModel(torch.nn.Module):
         files' size.  Under --graph_step the decode runs in front of the replay, as it does without the flag: the captured
         iteration reads the N x N buffers it is copied into."""
         size = self.resize_inputs or None
+        self._set_decoded(lambda: ops.decode_inputs(img1, img2, dep1, dep2, uv1, uv2, out_size=size), paths)
+
+    def _set_decoded(self, decode, paths=None):
+        """what follows the decode pass, whichever entry point ran it (`decode()` -> x_H1, x_H2, x_P, x_D): set_input_raw's
+        batch-fed pass, or set_input's slot-fed one on a resident batch"""
         if getattr(self, "_graph_state", "off") == "replay":
-            xh1, xh2, xp, xd = ops.decode_inputs(img1, img2, dep1, dep2, uv1, uv2, out_size=size)
+            xh1, xh2, xp, xd = decode()
             v, o = ops.nhwc_to_nchw_view, self.opt
             d = {"H1": v(xh1, o.H_input_nc), "H2": v(xh2, o.H_input_nc), "P1": v(xp)[:, : o.P_input_nc],
                  "P2": v(xp)[:, o.P_input_nc: 2 * o.P_input_nc], "D1": v(xd)[:, : o.D_input_nc],
@@ -617,7 +633,7 @@ class MMHandModel(torch.nn.Module):
             return self.set_input(d)
         for old in (getattr(self, "x_H1", None), getattr(self, "x_P", None), getattr(self, "x_D", None)):
             ops.pack_twin_drop(old)         # 16-bit copies a set_input() parked for the previous batch
-        self.x_H1, self.x_H2, self.x_P, self.x_D = ops.decode_inputs(img1, img2, dep1, dep2, uv1, uv2, out_size=size)
+        self.x_H1, self.x_H2, self.x_P, self.x_D = decode()
         v = ops.nhwc_to_nchw_view
         o = self.opt
         self.input_H1, self.input_H2 = v(self.x_H1, o.H_input_nc), v(self.x_H2, o.H_input_nc)

@@ -3243,3 +3243,54 @@ def decode_inputs(img1, img2, dep1, dep2, uv1, uv2, sigma=6.0, out_size=None):
     L.call("mmh_decode_inputs", _ptr(img1), _ptr(img2), _ptr(dep1), _ptr(dep2), _ptr(uv1), _ptr(uv2),
            B, H, W_, float(sigma), _ptr(xh1), _ptr(xh2), _ptr(xp), _ptr(xd), _stream())
     return xh1, xh2, xp, xd
+
+
+# --------------------------------------------------------------------------- resident dataset
+def _chk_store(store):
+    assert store.dtype == torch.uint8 and store.is_cuda and store.is_contiguous() and store.dim() == 4 and \
+        store.shape[0] >= 1 and store.shape[3] == 3, "store: contiguous uint8 CUDA [S,H,W,3], S >= 1"
+
+
+def _chk_status(status, dev):
+    assert status is None or (status.dtype == torch.int32 and status.device == dev and status.numel() == 1), \
+        "status: one int32 on the store's device"
+
+
+def store_images(src, slots, store, status=None):
+    """Scatter decoded images into a resident store (mmh_store_images): src uint8 [N,H,W,3] -> store uint8 [S,H,W,3] at
+    slots[n] (int32 [N] on the device); slot -1 skips the image.  A slot outside [-1, S) writes nothing and ORs 1 into
+    `status` (int32 [1]) when one is given."""
+    _chk_store(store)
+    S, H, W_, _ = store.shape
+    assert src.dtype == torch.uint8 and src.device == store.device and src.is_contiguous() and src.dim() == 4 and \
+        tuple(src.shape[1:]) == (H, W_, 3) and src.shape[0] >= 1, "src: contiguous uint8 [N,H,W,3] of the store's image size"
+    N = src.shape[0]
+    assert slots.dtype == torch.int32 and slots.device == store.device and slots.is_contiguous() and \
+        tuple(slots.shape) == (N,), "slots: contiguous int32 [N] on the store's device"
+    _chk_status(status, store.device)
+    L.call("mmh_store_images", _ptr(src), _ptr(slots), N, H, W_, _ptr(store), S, _ptr(status), _stream())
+
+
+def decode_inputs_indexed(store, idx, uv_table, out_size=None, sigma=6.0, status=None):
+    """decode_inputs with the sources read out of a resident store (mmh_decode_inputs_indexed): store uint8 [S,Hs,Ws,3] BGR,
+    idx int32 [B,4] = the slots of (img1, img2, dep1, dep2) of each sample, uv_table float64 [S,21,2] = every slot's joints
+    ALREADY on the output grid (resize_joints applied once, where the table is built) -> (xh1, xh2, xp, xd) as decode_inputs
+    returns them, bit for bit.  out_size None (or the store's own size) is the plain pass.  The slots are the caller's to
+    range-check on the host; the kernel writes zeros for a sample with a slot outside [0, S) and ORs 1 into `status`."""
+    _chk_store(store)
+    S, Hs, Ws, _ = store.shape
+    dev = store.device
+    assert idx.dtype == torch.int32 and idx.device == dev and idx.is_contiguous() and idx.dim() == 2 and \
+        idx.shape[0] >= 1 and idx.shape[1] == 4, "idx: contiguous int32 [B,4] on the store's device"
+    assert uv_table.dtype == torch.float64 and uv_table.device == dev and uv_table.is_contiguous() and \
+        tuple(uv_table.shape) == (S, 21, 2), "uv_table: contiguous float64 [S,21,2] on the store's device"
+    _chk_status(status, dev)
+    B = idx.shape[0]
+    Ho, Wo = resize_size(out_size, (Hs, Ws)) or (Hs, Ws)
+    xh1 = torch.empty((B, Ho, Wo, 4), dtype=torch.float32, device=dev)
+    xh2 = torch.empty((B, Ho, Wo, 4), dtype=torch.float32, device=dev)
+    xp = torch.empty((B, Ho, Wo, 44), dtype=torch.float32, device=dev)
+    xd = torch.empty((B, Ho, Wo, 8), dtype=torch.float32, device=dev)
+    L.call("mmh_decode_inputs_indexed", _ptr(store), S, Hs, Ws, _ptr(idx), _ptr(uv_table), B, Ho, Wo, float(sigma),
+           _ptr(xh1), _ptr(xh2), _ptr(xp), _ptr(xd), _ptr(status), _stream())
+    return xh1, xh2, xp, xd

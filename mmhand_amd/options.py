@@ -23,7 +23,9 @@ Differences, all deliberate:
     the default --L1_type l1_plus_perL1 refuses to start);
   * --resize_inputs N (addition; 0 = off): file-fed batches (--dataroot) reach the networks at N x N whatever size the
     files hold - the resize happens inside the device's decode pass (ops.decode_inputs).  --fineSize keeps the dead
-    meaning it has in the reference (declared, never read).
+    meaning it has in the reference (declared, never read);
+  * --resident_dataset / --resident_gb G (additions; off): the file-fed loader keeps the decoded dataset in device memory
+    after the first epoch (data.HandFolderLoader(resident=True)).
 """
 import argparse
 import os
@@ -96,6 +98,17 @@ _BASE = [
                              help="with --dataroot: feed the networks N x N images whatever size the files hold (0 = the "
                                   "files' size); bilinear with half-pixel centres inside the device's decode pass, joints "
                                   "scaled with it, sigma unchanged; N a multiple of 4")),
+    ("--resident_dataset", dict(action="store_true",
+                                help="with --dataroot: keep the decoded images of this rank's batches in device memory (the "
+                                     "loader's order never changes between epochs); the first epoch reads the files as usual and "
+                                     "fills the store, every later batch is one kernel reading it by index "
+                                     "(mmh_decode_inputs_indexed) - no file read, no PNG decode, no upload; "
+                                     "= MMH_RESIDENT_DATASET=1")),
+    ("--resident_gb", dict(type=float, default=64.0,
+                           help="with --resident_dataset: the most device memory the store may take, in GB (10^9 bytes).  The "
+                                "default is a policy choice - under a quarter of a 288 GB card - not a measured number; a "
+                                "dataset over it (or over the free memory) leaves the loader on the file path, whole: there "
+                                "is no partial store")),
 ]
 _TRAIN = [
     ("--display_freq", dict(type=int, default=100)),

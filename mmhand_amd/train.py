@@ -9,7 +9,9 @@ Same loop shape (epochs x batches, set_input + optimize_parameters, print/save c
 (annotation.pickle + colour / depth PNGs; data.HandFolderLoader, decoded on the device), else synthetic RHD/STB-shaped
 batches (`--synthetic_samples N` sets the epoch length).  `--resize_inputs N` with `--dataroot`: the networks train at
 N x N whatever size the files hold - the raw batches travel at the files' size and the device's decode pass writes N x N
-(MMHandModel.set_input; synthetic batches keep `--fineSize`)."""
+(MMHandModel.set_input; synthetic batches keep `--fineSize`).  `--resident_dataset` with `--dataroot`: the decoded images stay
+in device memory after the first epoch (at most `--resident_gb` GB of it) and every later batch is one kernel
+(data.HandFolderLoader(resident=True))."""
 import os
 import sys
 import time
