@@ -22,16 +22,10 @@
 // mode 1 runs the same kernel on dy with the flipped filter over the PADDED domain (zero padding 6) and folds the
 // pad ring back (transpose of ReflectionPad2d(3)) with fold7_kernel.
 #include <algorithm>
-#include "common.h"
+#include "device_prims.h"
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void* lds_vp;
-typedef const bf16x8 __attribute__((address_space(3))) * lds_frag_p;
-__device__ __forceinline__ bf16x8 lds_frag(unsigned addr) { return *reinterpret_cast<lds_frag_p>(addr); }
+using namespace mmh::dev;
 
 constexpr int TW = 16, TH = 8;                  // output tile
 template <int KS> struct Geo {                  // KS x KS taps (7: head / stems; 3: VGG conv1_1's image gradient)
@@ -56,14 +50,6 @@ struct C7KP {
     int TX, TY, tiles;
 };
 
-template <bool H16>
-__device__ __forceinline__ f32x4 mfma16(bf16x8 a, bf16x8 b, f32x4 c) {
-    if (H16)
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0,
-                                                      0, 0);
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-
 template <bool H16, int KS>
 __global__ void __launch_bounds__(256, 2) conv7_n4_kernel(const C7KP p) {
     typedef Geo<KS> G_;
@@ -73,8 +59,7 @@ __global__ void __launch_bounds__(256, 2) conv7_n4_kernel(const C7KP p) {
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l15 = lane & 15, g4 = lane >> 4;
     // one XCD walks a contiguous range of tiles (neighbouring tiles share halo rows in its L2)
-    const int per_xcd = (p.tiles + 7) / 8;
-    const int tile = (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
+    const int tile = xcd_item(p.tiles);
     if (tile >= p.tiles) return;
     const int b = tile / (p.TX * p.TY);
     const int trem = tile - b * (p.TX * p.TY);
@@ -111,7 +96,7 @@ __global__ void __launch_bounds__(256, 2) conv7_n4_kernel(const C7KP p) {
         }
     }
 
-    const unsigned lds0 = mmh::lds_addr_of(smem);
+    const unsigned lds0 = lds_addr_of(smem);
     // lane constants: the pixel fragment of tap column kw, k-half h, at this wave's first output row; the filter fragment
     unsigned aB[KS][2], wB[2];
 #pragma unroll
@@ -138,7 +123,7 @@ __global__ void __launch_bounds__(256, 2) conv7_n4_kernel(const C7KP p) {
 #pragma unroll
                 for (int i = 0; i < 2; ++i) {
                     const bf16x8 af = lds_frag(aB[kw][h] + (unsigned)((i + kh) * HPW * 128));
-                    acc[i] = mfma16<H16>(wf, af, acc[i]);
+                    acc[i] = mfma_16x16x32<H16>(wf, af, acc[i]);
                 }
             }
 
@@ -155,7 +140,7 @@ __global__ void __launch_bounds__(256, 2) conv7_n4_kernel(const C7KP p) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const float t = v[r] + bv[r];
-                    v[r] = p.act == MMH_ACT_RELU ? (t > 0.f ? t : 0.f) : (p.act == MMH_ACT_TANH ? tanhf(t) : t);
+                    v[r] = act_apply(t, p.act);
                 }
                 *reinterpret_cast<f32x4*>(p.y + ((size_t)(b * p.OH + oh) * p.OW + ow) * p.ycs) = v;
             }

@@ -21,15 +21,13 @@
 // into registers before the MFMAs of k-step i and written to LDS after them.
 #include <algorithm>
 #include <cstring>
-#include "common.h"
+#include "device_prims.h"
 
 namespace {
+using namespace mmh::dev;
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 // The 16-bit MFMA kernels serve two element types with one body: bf16 (MMH_BF16) and IEEE fp16
@@ -50,13 +48,6 @@ __device__ __forceinline__ bf16x4 to_lp4(float4 v) {
         return __builtin_bit_cast(bf16x4, r);
     }
     return to_bf16x4(v);
-}
-template <bool H16>
-__device__ __forceinline__ f32x16 mfma16(bf16x8 a, bf16x8 b, f32x16 c) {
-    if (H16)
-        return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0,
-                                                      0, 0);
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
 }
 // 4-channel element access of the Winograd-domain tensors: LP = 0 fp32 (float4), 1 bf16, 2 fp16
 // (8 bytes, RNE)
@@ -218,12 +209,6 @@ __device__ __forceinline__ unsigned gather_off(const Gather& g, unsigned img_bas
     }
     const unsigned off = ((img_base + (unsigned)(vh * g.srcW + vw)) * g.src_cs + (unsigned)s.c4 * 4u) * 4u;
     return ok ? off : OOB;
-}
-
-__device__ __forceinline__ float apply_act(float v, int act) {
-    if (act == MMH_ACT_RELU) return v > 0.f ? v : 0.f;
-    if (act == MMH_ACT_TANH) return tanhf(v);
-    return v;
 }
 
 // ---------------------------------------------------------------------------
@@ -569,7 +554,7 @@ __device__ __forceinline__ void conv_igemm_body(const ConvKP& p, const int bx, c
                 if (n < p.N) {
                     float v = acc[i][j][r] + bv[j];
                     if (p.accum) v += p.out[off + n];
-                    p.out[off + n] = apply_act(v, p.act);
+                    p.out[off + n] = act_apply(v, p.act);
                 }
             }
         }
@@ -1185,8 +1170,8 @@ __global__ void wino_output_kernel(const void* __restrict__ M, float* __restrict
     for (int r = 0; r < 2; ++r) {
         float4 y0 = f4add(f4add(f4add(s[r][0], s[r][1]), s[r][2]), bv);
         float4 y1 = f4add(f4sub(f4sub(s[r][1], s[r][2]), s[r][3]), bv);
-        y0 = make_float4(apply_act(y0.x, act), apply_act(y0.y, act), apply_act(y0.z, act), apply_act(y0.w, act));
-        y1 = make_float4(apply_act(y1.x, act), apply_act(y1.y, act), apply_act(y1.z, act), apply_act(y1.w, act));
+        y0 = make_float4(act_apply(y0.x, act), act_apply(y0.y, act), act_apply(y0.z, act), act_apply(y0.w, act));
+        y1 = make_float4(act_apply(y1.x, act), act_apply(y1.y, act), act_apply(y1.z, act), act_apply(y1.w, act));
         float4* o = reinterpret_cast<float4*>(y) + (((long long)b * H + 2 * ty + r) * W + 2 * tx) * C4 + c;
         o[0] = y0;
         o[C4] = y1;
@@ -1381,7 +1366,7 @@ __device__ __forceinline__ void conv_igemm_bf16_body_t(const ConvKP& p, const in
             for (int i = 0; i < TM; ++i)
 #pragma unroll
                 for (int jn = 0; jn < TN; ++jn)
-                    acc[i][jn] = mfma16<H16>(af[i], bfr[jn], acc[i][jn]);
+                    acc[i][jn] = mfma_32x32x16<H16>(af[i], bfr[jn], acc[i][jn]);
         }
         if (!(p.dbg & 2)) {
             __syncthreads();
@@ -1418,7 +1403,7 @@ __device__ __forceinline__ void conv_igemm_bf16_body_t(const ConvKP& p, const in
                 if (n < p.N) {
                     float v = acc[i][jn][r] + bv[jn];
                     if (p.accum) v += p.out[off + n];
-                    p.out[off + n] = apply_act(v, p.act);
+                    p.out[off + n] = act_apply(v, p.act);
                 }
             }
         }
@@ -1707,7 +1692,6 @@ __global__ void __launch_bounds__(256, 2) conv_wgrad_kernel(const WgradKP p) {
 // order they arrive in, channel contiguous) and the 32x32x16 operands need 8 consecutive pixels
 // per lane.  Row pitch 320 B puts the 4 rows of a transposed 4x16 block on disjoint banks.
 // ---------------------------------------------------------------------------
-typedef short s16x4 __attribute__((ext_vector_type(4)));
 constexpr int BKP = 64;      // pixels per k-step
 constexpr int LDT = 160;     // LDS row pitch in bf16 elements (128 + 32 pad = 320 B)
 
@@ -1857,7 +1841,7 @@ __device__ __forceinline__ void conv_wgrad_bf16_body(const WgradKP& p) {
                 for (int i = 0; i < TM; ++i)
 #pragma unroll
                     for (int j = 0; j < TN; ++j)
-                        acc[i][j] = mfma16<H16>(af[i], bfr[j], acc[i][j]);
+                        acc[i][j] = mfma_32x32x16<H16>(af[i], bfr[j], acc[i][j]);
             }
             __syncthreads();
             if (more) store_tiles();
@@ -2011,7 +1995,7 @@ __global__ void __launch_bounds__(256, 2) wino_gemm_bf16_kernel(const WinoGemmBf
                 for (int i = 0; i < TM; ++i)
 #pragma unroll
                     for (int j = 0; j < TN; ++j)
-                        acc[i][j] = mfma16<H16>(af[i], bfr[j], acc[i][j]);
+                        acc[i][j] = mfma_32x32x16<H16>(af[i], bfr[j], acc[i][j]);
             }
             if (ks == KS - 1) {
                 const int nt = wc % p.NT;
@@ -2164,7 +2148,7 @@ __global__ void __launch_bounds__(256, 2) wino_wgrad_gemm_bf16_kernel(const Wino
                 for (int i = 0; i < TM; ++i)
 #pragma unroll
                     for (int j = 0; j < TN; ++j)
-                        acc[i][j] = mfma16<H16>(af[i], bfr[j], acc[i][j]);
+                        acc[i][j] = mfma_32x32x16<H16>(af[i], bfr[j], acc[i][j]);
             }
             if (ks == KS - 1) {
                 const int nt = wc % p.NT;
@@ -2912,7 +2896,7 @@ __global__ void wino4_output_kernel(const float* __restrict__ M, float* __restri
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             F2 v = o4[q] + bv;
-            v.x = apply_act(v.x, act); v.y = apply_act(v.y, act);
+            v.x = act_apply(v.x, act); v.y = act_apply(v.y, act);
             yo[(((long long)b * H + 4 * ty + r) * W + 4 * tx + q) * C2 + c] = v;
         }
     }

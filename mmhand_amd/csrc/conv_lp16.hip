@@ -5,7 +5,7 @@
 //   * BOTH operands are 16-bit in HBM with the contraction index contiguous - activations
 //     [B][H][W][C] (a 16-bit twin written by the producer or by mmh_cvt_lp16), weights
 //     [tap][N][K] (mmh_prep_weights_bf16/_fp16) - so both go global -> LDS by LDS-DMA
-//     (global_load_lds_dwordx4, 1 KiB per wave instruction, no VGPR staging, no ds_write);
+//     (lds_dma16, 1 KiB per wave instruction, no VGPR staging, no ds_write);
 //   * 256 x 256 x 64 block tile, 512 threads = 8 waves as 2 (M) x 4 (N), wave tile 128 x 64 =
 //     4 x 2 MFMA 32x32x16 tiles (128 accumulator VGPRs): 32 B/clk/CU of L2 traffic at the full
 //     MFMA rate (the 128^2 tile needs 64);
@@ -26,15 +26,7 @@
 
 namespace {
 using namespace mmh::lp16;
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-template <bool H16>
-__device__ __forceinline__ f32x16 mfma16(bf16x8 a, bf16x8 b, f32x16 c) {        // 32x32x16: the flat-row wgrad below
-    if (H16)
-        return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0,
-                                                      0, 0);
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
+using namespace mmh::dev;
 
 // conv_lp16p_kernel: the row-tile form (256 consecutive output pixels x 256 channels, the activation tile re-staged per tap) on
 // the 16x16x32 MFMA - wave tile 128 x 64 = 8 x 4 tiles of 16x16, 4 accumulator VGPRs each; A / B fragment of lane l: row
@@ -54,8 +46,7 @@ __global__ void __launch_bounds__(512, 2) conv_lp16p_kernel(const LpConvKP p) {
     const int lane = tid & 63, wave = tid >> 6;
     const int l15 = lane & 15, g4 = lane >> 4;
     const int wr = wave >> 2, wc = wave & 3;
-    const int per_xcd = (p.MT * p.NT + 7) / 8;
-    const int tile = (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
+    const int tile = xcd_item(p.MT * p.NT);
     if (tile >= p.MT * p.NT) return;
     const int mt = tile / p.NT, nt = tile - mt * p.NT;
     const int m0 = mt * TBM, n0 = nt * TBN;
@@ -155,7 +146,7 @@ __global__ void __launch_bounds__(512, 2) conv_lp16p_kernel(const LpConvKP p) {
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
 #pragma unroll
-            for (int j = 0; j < 4; ++j) acc[i][j] = mfma16s<H16>(af[i], b0[j], acc[i][j]);
+            for (int j = 0; j < 4; ++j) acc[i][j] = mfma_16x16x32<H16>(af[i], b0[j], acc[i][j]);
             af[i] = *reinterpret_cast<const bf16x8*>(st + a_base + sw1 + i * (16 * ROWB));
         }
 #pragma unroll
@@ -177,7 +168,7 @@ __global__ void __launch_bounds__(512, 2) conv_lp16p_kernel(const LpConvKP p) {
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
 #pragma unroll
-            for (int j = 0; j < 4; ++j) acc[i][j] = mfma16s<H16>(af[i], b1[j], acc[i][j]);
+            for (int j = 0; j < 4; ++j) acc[i][j] = mfma_16x16x32<H16>(af[i], b1[j], acc[i][j]);
             if (more) af[i] = *reinterpret_cast<const bf16x8*>(sn + a_base + sw0 + i * (16 * ROWB));
         }
 #pragma unroll
@@ -259,8 +250,7 @@ __device__ __forceinline__ void conv_lp16g_body(const LpGConvKP& p) {
     const int lane = tid & 63, wave = tid >> 6;
     const int l15 = lane & 15, g4 = lane >> 4;
     const int wr = wave >> 2, wc = wave & 3;
-    const int per_xcd = (p.MT * p.NT + 7) / 8;
-    const int tile = (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
+    const int tile = xcd_item(p.MT * p.NT);
     if (tile >= p.MT * p.NT) return;
     const int mt = tile / p.NT, nt = tile - mt * p.NT;
     const int m0 = mt * TBM, n0 = nt * BNT;
@@ -380,7 +370,7 @@ __device__ __forceinline__ void conv_lp16g_body(const LpGConvKP& p) {
 #pragma unroll
             for (int i = 0; i < 8; ++i)
 #pragma unroll
-                for (int j = 0; j < NJ; ++j) acc[i][j] = mfma16s<H16>(bfr[j], af[i], acc[i][j]);
+                for (int j = 0; j < NJ; ++j) acc[i][j] = mfma_16x16x32<H16>(bfr[j], af[i], acc[i][j]);
             __builtin_amdgcn_s_setprio(0);
             __builtin_amdgcn_sched_barrier(0);
         }
@@ -393,7 +383,7 @@ __device__ __forceinline__ void conv_lp16g_body(const LpGConvKP& p) {
     for (int j = 0; j < NJ; ++j)
 #pragma unroll
         for (int r = 0; r < 4; ++r) bv[j][r] = p.bias ? p.bias[n0 + wc * (BNT / 4) + j * 16 + 4 * g4 + r] : 0.f;
-    if (p.y16 && NJ % 2 == 0 && p.st16) {      // 16-byte stores after the lane-pair trade (common.h: pair_swap8)
+    if (p.y16 && NJ % 2 == 0 && p.st16) {      // 16-byte stores after the lane-pair trade (device_prims.h: pair_swap8)
         const int cb0 = ((g4 & 1) ? 16 : 0) + 4 * (g4 & 2);
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
@@ -406,13 +396,13 @@ __device__ __forceinline__ void conv_lp16g_body(const LpGConvKP& p) {
 #pragma unroll
             for (int jp = 0; jp < NJ / 2; ++jp) {
                 float v[8];
-                mmh::pair_swap8(acc[i][2 * jp], acc[i][2 * jp + (NJ > 1 ? 1 : 0)], v);
+                pair_swap8(acc[i][2 * jp], acc[i][2 * jp + (NJ > 1 ? 1 : 0)], v);
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
                     const float t = v[e] + (p.bias ? p.bias[n0 + wc * (BNT / 4) + jp * 32 + cb0 + e] : 0.f);
-                    v[e] = p.act == MMH_ACT_RELU ? (t > 0.f ? t : 0.f) : (p.act == MMH_ACT_TANH ? tanhf(t) : t);
+                    v[e] = act_apply(t, p.act);
                 }
-                if (m < M) mmh::store8_lp16<H16>(p.y16 + (opix * p.y_cs + (n0 + wc * (BNT / 4) + jp * 32 + cb0)) * 2, v);
+                if (m < M) store8_lp16<H16>(p.y16 + (opix * p.y_cs + (n0 + wc * (BNT / 4) + jp * 32 + cb0)) * 2, v);
             }
         }
         return;
@@ -459,8 +449,7 @@ __global__ void __launch_bounds__(512, 2) conv_lp16f_kernel(const LpFlatKP p) {
     const int tid = threadIdx.x;
     const int lane = tid & 63, wave = tid >> 6;
     const int l15 = lane & 15, g4 = lane >> 4;
-    const int per_xcd = (p.MT * p.NT + 7) / 8;
-    const int tile = (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
+    const int tile = xcd_item(p.MT * p.NT);
     if (tile >= p.MT * p.NT) return;
     const int mt = tile / p.NT, nt = tile - mt * p.NT;
     const int m0 = mt * TBM, n0 = nt * 64;
@@ -544,7 +533,7 @@ __global__ void __launch_bounds__(512, 2) conv_lp16f_kernel(const LpFlatKP p) {
 #pragma unroll
             for (int i = 0; i < 2; ++i)
 #pragma unroll
-                for (int j = 0; j < 4; ++j) acc[i][j] = mfma16s<H16>(bfr[j], af[i], acc[i][j]);
+                for (int j = 0; j < 4; ++j) acc[i][j] = mfma_16x16x32<H16>(bfr[j], af[i], acc[i][j]);
         }
     }
 
@@ -637,7 +626,6 @@ MMH_LPG_KERNEL(64)
 
 // transposed reads of [pixel][256 channels] LDS images (ds_read_b64_tr_b16) for the flat-row wgrad below
 constexpr int WROWB = 512;                      // bytes per LDS row: 256 channels
-typedef short s16x4 __attribute__((ext_vector_type(4)));
 
 // Operand fragment for lane: 8 consecutive rows (pixels) row0 + 8h .. of column col0 + (lane & 31) from a
 // [pixel][256 channels] image with the chunk swizzle above.  tr_off() is the lane's byte offset for
@@ -688,8 +676,7 @@ __device__ __forceinline__ void wgrad_lp16f_body(const LpWgradFKP& p) {
     const int lane = tid & 63, wave = tid >> 6;
     const int l31 = lane & 31, h = lane >> 5;
     const int wm = wave / WN, wn = wave % WN;
-    const int per_xcd = (p.items + 7) / 8;
-    int item = (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
+    int item = xcd_item(p.items);
     if (item >= p.items) return;
     const int mt = item % p.MT; item /= p.MT;       // row tiles fastest: they share the dy tile and the x pixels
     const int nt = item % p.NT;
@@ -743,8 +730,8 @@ __device__ __forceinline__ void wgrad_lp16f_body(const LpWgradFKP& p) {
             const size_t src = ((size_t)pimg[j] * p.H + ih) * p.W + iw;
             const char* gx = okx ? p.x + src * p.x_cs * 2 + x_coff[j] : p.zeros + (lane & 31) * 16;
             const char* gd = (ok && d_ok[j]) ? p.dy + (size_t)pix[j] * p.dy_cs * 2 + d_coff[j] : p.zeros + (lane & 31) * 16;
-            mmh::lds_dma16(gx, __builtin_amdgcn_readfirstlane(mmh::lds_addr_of(sX + (wave * 2 + j) * 1024)));
-            mmh::lds_dma16(gd, __builtin_amdgcn_readfirstlane(mmh::lds_addr_of(sD + (wave * 2 + j) * 1024)));
+            lds_dma16(gx, __builtin_amdgcn_readfirstlane(lds_addr_of(sX + (wave * 2 + j) * 1024)));
+            lds_dma16(gd, __builtin_amdgcn_readfirstlane(lds_addr_of(sD + (wave * 2 + j) * 1024)));
             pix[j] += 32;
             pow_[j] += 32;
             while (pow_[j] >= p.Wo) {
@@ -780,7 +767,7 @@ __device__ __forceinline__ void wgrad_lp16f_body(const LpWgradFKP& p) {
 #pragma unroll
         for (int i = 0; i < TM; ++i)
 #pragma unroll
-            for (int j = 0; j < TN; ++j) acc[i][j] = mfma16<H16>(af[buf][i], bfr[buf][j], acc[i][j]);
+            for (int j = 0; j < TN; ++j) acc[i][j] = mfma_32x32x16<H16>(af[buf][i], bfr[buf][j], acc[i][j]);
     };
     if (k0 < k1) { issue_half(); issue_half(); issue_half(); }
     int slot = 0;

@@ -13,6 +13,7 @@
 
 namespace {
 using namespace mmh::lp16;
+using namespace mmh::dev;
 
 // ---------------------------------------------------------------------------------------------
 // conv_lp16h2_kernel: conv_lp16h_kernel with the fragment ADDRESS arithmetic taken out of the k-loop.
@@ -213,7 +214,7 @@ __device__ __forceinline__ void conv_lp16h2_body(const LpConvKP& p) {
 
     // lane-constant LDS byte addresses (32-bit) of stage 0: A [dw][half], B [half]; the k-step adds the stage offset
     // and dh rows (scalars), the fragment index i an immediate
-    const unsigned lds0 = mmh::lds_addr_of(smem);
+    const unsigned lds0 = lds_addr_of(smem);
     // (named scalars, not an array: a select over array elements comes back from the compiler as a run-time indexed
     // load from a SCRATCH copy of the array)
     auto a_lane = [&](int dw, int hf) -> unsigned {
@@ -345,7 +346,7 @@ __device__ __forceinline__ void conv_lp16h2_body(const LpConvKP& p) {
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
 #pragma unroll
-                for (int j = 0; j < NJ; ++j) acc[i][j] = mfma16s<H16>(b0[j], af[i], acc[i][j]);
+                for (int j = 0; j < NJ; ++j) acc[i][j] = mfma_16x16x32<H16>(b0[j], af[i], acc[i][j]);
                 af[i] = lds_frag(a1 + i * (HP2 * ROWB));
             }
 #pragma unroll
@@ -367,7 +368,7 @@ __device__ __forceinline__ void conv_lp16h2_body(const LpConvKP& p) {
 #pragma unroll
             for (int j = 0; j < NJ; ++j) {
                 if (SOLO) mfma16s_vgpr<H16>(FA[j], b0[j], axf);
-                else FA[j] = mfma16s<H16>(b0[j], axf, FA[j]);
+                else FA[j] = mfma_16x16x32<H16>(b0[j], axf, FA[j]);
             }
             if (do_cnr) {         // once per chunk in the four corner tiles: not worth registers for a prefetch
                 axf = lds_frag((kw == 0 ? aA00 : aA20) + f_st + f_rsel);
@@ -376,7 +377,7 @@ __device__ __forceinline__ void conv_lp16h2_body(const LpConvKP& p) {
 #pragma unroll
                 for (int j = 0; j < NJ; ++j) {
                     if (SOLO) mfma16s_vgpr<H16>(FA[j], b0[j], axf);
-                    else FA[j] = mfma16s<H16>(b0[j], axf, FA[j]);
+                    else FA[j] = mfma_16x16x32<H16>(b0[j], axf, FA[j]);
                 }
             }
         }
@@ -426,7 +427,7 @@ __device__ __forceinline__ void conv_lp16h2_body(const LpConvKP& p) {
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
 #pragma unroll
-                for (int j = 0; j < NJ; ++j) acc[i][j] = mfma16s<H16>(b1[j], af[i], acc[i][j]);
+                for (int j = 0; j < NJ; ++j) acc[i][j] = mfma_16x16x32<H16>(b1[j], af[i], acc[i][j]);
                 af[i] = lds_frag(a0n + i * (HP2 * ROWB));
             }
 #pragma unroll
@@ -438,7 +439,7 @@ __device__ __forceinline__ void conv_lp16h2_body(const LpConvKP& p) {
 #pragma unroll
             for (int i = 4; i < 8; ++i) {
 #pragma unroll
-                for (int j = 0; j < NJ; ++j) acc[i][j] = mfma16s<H16>(b1[j], af[i], acc[i][j]);
+                for (int j = 0; j < NJ; ++j) acc[i][j] = mfma_16x16x32<H16>(b1[j], af[i], acc[i][j]);
                 af[i] = lds_frag(a0n + i * (HP2 * ROWB));
             }
 #pragma unroll
@@ -478,7 +479,7 @@ __device__ __forceinline__ void conv_lp16h2_body(const LpConvKP& p) {
 #pragma unroll
             for (int j = 0; j < NJ; ++j) {
                 if (SOLO) mfma16s_vgpr<H16>(FA[j], b1[j], axf);
-                else FA[j] = mfma16s<H16>(b1[j], axf, FA[j]);
+                else FA[j] = mfma_16x16x32<H16>(b1[j], axf, FA[j]);
             }
             if (do_cnr) {
                 axf = lds_frag(((kw == 0 ? aA00 : aA20) + f_st + f_rsel) ^ 64u);
@@ -487,7 +488,7 @@ __device__ __forceinline__ void conv_lp16h2_body(const LpConvKP& p) {
 #pragma unroll
                 for (int j = 0; j < NJ; ++j) {
                     if (SOLO) mfma16s_vgpr<H16>(FA[j], b1[j], axf);
-                    else FA[j] = mfma16s<H16>(b1[j], axf, FA[j]);
+                    else FA[j] = mfma_16x16x32<H16>(b1[j], axf, FA[j]);
                 }
             }
         }
@@ -559,7 +560,7 @@ __device__ __forceinline__ void conv_lp16h2_body(const LpConvKP& p) {
         else body(std::integral_constant<int, MMH_ACT_NONE>{});
     };
     if (p.y16 && !(p.dbg & 128)) {
-        // 16-bit output: 16-byte stores after the lane-pair trade (common.h: pair_swap8) - 16 store instructions per tile
+        // 16-bit output: 16-byte stores after the lane-pair trade (device_prims.h: pair_swap8) - 16 store instructions per tile
         // instead of 32; 256 -> 256 fprop 150 -> 134 us, the 16-bit step 102.5 -> 100.8 ms (tools/ab_lp16_stores.py;
         // mmh_set_option("lp16_dbg", 128) = 8-byte stores)
         const bool odd = (g4 & 1) != 0;
@@ -584,18 +585,18 @@ __device__ __forceinline__ void conv_lp16h2_body(const LpConvKP& p) {
             {
                 const size_t e00 = (((size_t)b * p.H + (oh0 + wr * 8)) * p.W + ow) * p.N + (size_t)(n0 + wc * WCH + cb0);
                 const size_t erow = (size_t)p.W * p.N;
-                const unsigned nb0 = __builtin_amdgcn_readfirstlane(mmh::lds_addr_of(nbx));
+                const unsigned nb0 = __builtin_amdgcn_readfirstlane(lds_addr_of(nbx));
                 asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");      // every wave is done reading LDS
 #pragma unroll
                 for (int i = 0; i < 8; ++i)
 #pragma unroll
                     for (int jp = 0; jp < NJ / 2; ++jp)
-                        mmh::lds_dma16(p.nbr_x + (e00 + i * erow + jp * 32) * 2, nb0 + (unsigned)(i * (NJ / 2) + jp) * 1024u);
+                        lds_dma16(p.nbr_x + (e00 + i * erow + jp * 32) * 2, nb0 + (unsigned)(i * (NJ / 2) + jp) * 1024u);
                 if (p.nbr_bits) {
                     const size_t k00 = (((size_t)b * p.H + (oh0 + wr * 8 + g4)) * p.W + ow) * p.N + (size_t)(n0 + wc * WCH);
 #pragma unroll
                     for (int q = 0; q < 2; ++q)
-                        mmh::lds_dma16(p.nbr_bits + ((k00 + (size_t)(4 * q) * erow) >> 3), nb0 + 16384u + (unsigned)q * 1024u);
+                        lds_dma16(p.nbr_bits + ((k00 + (size_t)(4 * q) * erow) >> 3), nb0 + 16384u + (unsigned)q * 1024u);
                 }
             }
 #pragma unroll
@@ -604,8 +605,8 @@ __device__ __forceinline__ void conv_lp16h2_body(const LpConvKP& p) {
 #pragma unroll
                 for (int jp = 0; jp < NJ / 2; ++jp) {
                     float v[8];
-                    mmh::pair_swap8(acc[i][2 * jp], acc[i][2 * jp + 1], v);
-                    mmh::store8_lp16<H16>(p.y16 + (m * p.y_cs + (n0 + wc * WCH + jp * 32 + cb0)) * 2, v);
+                    pair_swap8(acc[i][2 * jp], acc[i][2 * jp + 1], v);
+                    store8_lp16<H16>(p.y16 + (m * p.y_cs + (n0 + wc * WCH + jp * 32 + cb0)) * 2, v);
                 }
             }
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // the DMA above has landed (this wave reads only its own)
@@ -620,7 +621,7 @@ __device__ __forceinline__ void conv_lp16h2_body(const LpConvKP& p) {
 #pragma unroll
                 for (int i = 0; i < 8; ++i) {
                     float v[8];
-                    mmh::pair_swap8(acc[i][2 * jp], acc[i][2 * jp + 1], v);
+                    pair_swap8(acc[i][2 * jp], acc[i][2 * jp + 1], v);
                     const uint4 xr = *reinterpret_cast<const uint4*>(nbx + (i * (NJ / 2) + jp) * 1024 + lane * 16);
                     const unsigned xw[4] = {xr.x, xr.y, xr.z, xr.w};
                     const unsigned kb = p.nbr_bits ? *reinterpret_cast<const unsigned short*>(
@@ -675,14 +676,14 @@ __device__ __forceinline__ void conv_lp16h2_body(const LpConvKP& p) {
 #pragma unroll
                 for (int jp = 0; jp < NJ / 2; ++jp) {
                     float v[8];
-                    mmh::pair_swap8(acc[i][2 * jp], acc[i][2 * jp + 1], v);
+                    pair_swap8(acc[i][2 * jp], acc[i][2 * jp + 1], v);
 #pragma unroll
                     for (int e = 0; e < 8; ++e) {
                         const float t = v[e] + (p.bias ? p.bias[n0 + wc * WCH + jp * 32 + cb0 + e] : 0.f);
-                        v[e] = ACT == MMH_ACT_RELU ? (t > 0.f ? t : 0.f) : (ACT == MMH_ACT_TANH ? tanhf(t) : t);
+                        v[e] = act_apply(t, ACT);
                     }
                     if (oh < p.H && ow < p.W) {
-                        mmh::store8_lp16<H16>(p.y16 + (m * p.y_cs + (n0 + wc * WCH + jp * 32 + cb0)) * 2, v);
+                        store8_lp16<H16>(p.y16 + (m * p.y_cs + (n0 + wc * WCH + jp * 32 + cb0)) * 2, v);
                     }
                 }
             }

@@ -24,15 +24,12 @@
 // HBM floor of 64 -> 128 at B = 32: 268 MB in + 134 MB out = 67 us at 6 TB/s = 0.46 of the bf16 peak - these convs are
 // close to memory-bound at the rates the kernel is built for.
 #include <algorithm>
-#include "common.h"
+#include "device_prims.h"
 
 namespace mmh { int g_lp16_s2f = 1; }       // mmh_set_option("lp16_s2f", 0): the general kernel (A/B); 2: also for 128 input channels
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using namespace mmh::dev;
 
 constexpr int TH = 8, TW = 16;                  // output tile
 constexpr int ODD0 = 17;                        // stride 2: first slot of the odd columns (halo 17 x 33 input pixels in 34-slot
@@ -55,38 +52,6 @@ struct S2KP {
     int rev;                // taps mirrored (w = the plain copy [tap][Cin][Cout]: the input gradient of a stride-1 conv)
     int dbg;                // timing-only ablations (mmh_set_option "lp16_dbg"; results wrong): 1 no halo DMA after the first, 2 no MFMAs
 };
-
-template <bool H16>
-__device__ __forceinline__ f32x4 mfma(bf16x8 a, bf16x8 b, f32x4 c) {
-    if (H16)
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-
-template <bool H16>
-__device__ __forceinline__ void store4(float* y, char* y16, size_t elem, f32x4 v, const float* bv, int act) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const float t = v[r] + bv[r];
-        v[r] = act == MMH_ACT_RELU ? (t > 0.f ? t : 0.f) : (act == MMH_ACT_TANH ? tanhf(t) : t);
-    }
-    if (y16) {
-        if (H16) {
-            typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-            const h4 o = {(_Float16)v[0], (_Float16)v[1], (_Float16)v[2], (_Float16)v[3]};
-            *reinterpret_cast<h4*>(y16 + elem * 2) = o;
-        } else {
-            typedef __bf16 b4 __attribute__((ext_vector_type(4)));
-            const b4 o = {(__bf16)v[0], (__bf16)v[1], (__bf16)v[2], (__bf16)v[3]};
-            *reinterpret_cast<b4*>(y16 + elem * 2) = o;
-        }
-    } else {
-        *reinterpret_cast<f32x4*>(y + elem) = v;
-    }
-}
-
-typedef const bf16x8 __attribute__((address_space(3))) * lds_frag_p;
-__device__ __forceinline__ bf16x8 lds_frag(unsigned addr) { return *reinterpret_cast<lds_frag_p>(addr); }
 
 // The halo of an 8 x 16 output tile under image stride S: S = 2 as above (de-interleaved rows); S = 1 (the stride-1 form of the
 // same kernel: VGG19's conv1_2, 64 -> 64 at full resolution, losses/L1_plus_perceptualLoss.py:22-27 - on the general
@@ -142,7 +107,7 @@ __global__ void __launch_bounds__(512) conv_s2f_kernel(const S2KP p) {
     // halo DMA roles: round rd moves LDS rows rd * 64 + wave * 8 + lane / 8 (row = hy * PITCH + slot), 16-byte chunk lane & 7
     // of the row = global chunk (lane & 7) ^ (slot & 6).  The source offsets are computed where the chunk is issued (once
     // per 72 KB of DMA) and not kept: ten registers the resident weights need more
-    const unsigned lds0 = mmh::lds_addr_of(smem);
+    const unsigned lds0 = lds_addr_of(smem);
     auto issue_chunk = [&](int tile, int kc, int buf) {
         const int b = tile / (p.TX * p.TY);
         const int rem = tile - b * (p.TX * p.TY);
@@ -162,7 +127,7 @@ __global__ void __launch_bounds__(512) conv_s2f_kernel(const S2KP p) {
             if (row) {
                 const char* g = ok ? xb + ((size_t)((unsigned)((b * p.H + ih) * p.W + iw) * (unsigned)p.cs * 2u + q8 * 16u))
                                    : p.zeros + (lane & 7) * 16;
-                mmh::lds_dma16(g, (unsigned)__builtin_amdgcn_readfirstlane((int)(dst + (unsigned)rd * 8192u)));
+                lds_dma16(g, (unsigned)__builtin_amdgcn_readfirstlane((int)(dst + (unsigned)rd * 8192u)));
             }
         }
     };
@@ -227,7 +192,7 @@ __global__ void __launch_bounds__(512) conv_s2f_kernel(const S2KP p) {
                 for (int i = 0; i < RB; ++i)
 #pragma unroll
                     for (int j = 0; j < NJ; ++j)
-                        acc[rh * RB + i][j] = mfma<H16>(wf[tap][2 * kc + hf][j], af[blk & 1][i], acc[rh * RB + i][j]);
+                        acc[rh * RB + i][j] = mfma_16x16x32<H16>(wf[tap][2 * kc + hf][j], af[blk & 1][i], acc[rh * RB + i][j]);
                 if (blk + 1 < NBLK) __builtin_amdgcn_sched_group_barrier(0x100, RB, 0);
                 __builtin_amdgcn_sched_group_barrier(0x008, RB * NJ, 0);
             }
@@ -236,7 +201,7 @@ __global__ void __launch_bounds__(512) conv_s2f_kernel(const S2KP p) {
         }
         // epilogue: lane (l15, g4) holds channels 4 g4 .. + 3 of pixel l15 of each of its rows, in each of its NJ column tiles
         // (tried: the lanes g4 / g4 ^ 1 trading one accumulator each so that a lane stores 16 bytes - half the store
-        // instructions, what gives conv_lp16h2_kernel 11 % at 256 -> 256 (common.h: pair_swap8) - ran 152 us (__shfl_xor) and
+        // instructions, what gives conv_lp16h2_kernel 11 % at 256 -> 256 (device_prims.h: pair_swap8) - ran 152 us (__shfl_xor) and
         // 163 us (v_permlane16_swap) against 116: tools/bench_s2f.py; and in the stride-1 form, which has registers to spare,
         // 246 us against 210: tools/bench_s1f.py)
         const int b = tile / (p.TX * p.TY);
@@ -251,10 +216,10 @@ __global__ void __launch_bounds__(512) conv_s2f_kernel(const S2KP p) {
                     store4<H16>(p.y, p.y16, pix * p.y_cs + (n0 + 16 * j + 4 * g4), acc[i][j], bv[j], p.act);
             }
         }
-        if (STATS) {        // the InstanceNorm behind this conv merges these partials instead of reading y (common.h)
+        if (STATS) {        // the InstanceNorm behind this conv merges these partials instead of reading y (device_prims.h: wave_tile_stats)
             const int chunks = p.TX * p.TY * MW;
             float* sp = p.stats + ((size_t)(b * chunks + (ty * p.TX + tx) * MW + wm) * 3) * p.N + n0 + 4 * g4;
-            mmh::wave_tile_stats<MI, NJ>([&](int i, int j, int r) {
+            wave_tile_stats<MI, NJ>([&](int i, int j, int r) {
                 const float t = acc[i][j][r] + bv[j][r];
                 return H16 ? (float)(_Float16)t : (float)(__bf16)t;
             }, l15, sp, p.N);
@@ -337,7 +302,7 @@ __device__ __forceinline__ void conv_s2d_body(const S2DKP& p, char* smem, int la
 #pragma unroll
     for (int r = 0; r < 4; ++r) bv[r] = p.bias ? p.bias[n0 + 4 * g4 + r] : 0.f;
 
-    const unsigned lds0 = mmh::lds_addr_of(smem);
+    const unsigned lds0 = lds_addr_of(smem);
     auto issue_tile = [&](int tile, int buf) {      // both 64-channel chunks of the tile's dy halo
         const int b = tile / (p.TX * p.TY);
         const int rem = tile - b * (p.TX * p.TY);
@@ -356,7 +321,7 @@ __device__ __forceinline__ void conv_s2d_body(const S2DKP& p, char* smem, int la
                 if (row) {
                     const char* gsrc = ok ? p.g + ((size_t)((unsigned)((b * p.Ho + ph) * p.Wo + qw) * (unsigned)p.cs * 2u) + kc * 128 + q8 * 16u)
                                           : p.zeros + (lane & 7) * 16;
-                    mmh::lds_dma16(gsrc, (unsigned)__builtin_amdgcn_readfirstlane((int)(dst + (unsigned)rd * 8192u)));
+                    lds_dma16(gsrc, (unsigned)__builtin_amdgcn_readfirstlane((int)(dst + (unsigned)rd * 8192u)));
                 }
             }
         }
@@ -410,7 +375,7 @@ __device__ __forceinline__ void conv_s2d_body(const S2DKP& p, char* smem, int la
                     if (L > prev_hi && L <= hi) { load_slot(L); nload += (TYPE == 0 || (L % 9) != TH) ? 2 : 1; }
 #pragma unroll
                 for (int t = 0; t < T::N; ++t)
-                    acc[T::slot[t]][i] = mfma<H16>(wf[t][k], R[(base + T::dh[t]) & 3][T::dw[t]], acc[T::slot[t]][i]);
+                    acc[T::slot[t]][i] = mfma_16x16x32<H16>(wf[t][k], R[(base + T::dh[t]) & 3][T::dw[t]], acc[T::slot[t]][i]);
                 if (nload == 4) __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
                 else if (nload == 3) __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);
                 else if (nload == 2) __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);

@@ -14,12 +14,11 @@
 //     interleaved row blocks), contraction over the pixels, split-K over tile ranges into fp32 slabs summed
 //     in a fixed order (deterministic).
 // Each input element is read 7 times (once per filter row), not 49.
-#include "common.h"
+#include "device_prims.h"
 
 namespace {
+using namespace mmh::dev;
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f4 __attribute__((ext_vector_type(4)));     // (HIP's float4 class kept the prefetch registers in scratch)
 constexpr int TR = 2;           // image rows per tile
 constexpr int TC = 64;          // image columns per tile
 constexpr int XC = TC + 6;      // padded columns per staged row
@@ -90,7 +89,7 @@ __global__ void __launch_bounds__(256) stem_wgrad_kernel(const StemWgKP p) {
         aoff[i] = khl * xrow + (m - khl * p.run);
     }
 
-    f4 rx[NXMAX], rd[8];
+    f32x4 rx[NXMAX], rd[8];     // (HIP's float4 class kept the prefetch registers in scratch)
     const long long rowstep4 = (long long)Wp * p.Cin / 4, drow4 = (long long)p.W * 16;
     int xoff[NXMAX];
     bool xok[NXMAX];
@@ -112,17 +111,17 @@ __global__ void __launch_bounds__(256) stem_wgrad_kernel(const StemWgKP p) {
     {                                                                                                            \
         const int t_ = (T_);                                                                                     \
         const int wx = t_ % tw, hy = (t_ / tw) % th, b = t_ / (tw * th);                                         \
-        const f4* xsrc = reinterpret_cast<const f4*>(                                                            \
+        const f32x4* xsrc = reinterpret_cast<const f32x4*>(                                                      \
             p.xp + (((long long)b * Hp + hy * TR + kh0) * Wp + wx * TC) * p.Cin);                                \
-        const f4* dsrc = reinterpret_cast<const f4*>(p.dy + (((long long)b * p.H + hy * TR) * p.W + wx * TC) * 64); \
+        const f32x4* dsrc = reinterpret_cast<const f32x4*>(p.dy + (((long long)b * p.H + hy * TR) * p.W + wx * TC) * 64); \
         _Pragma("unroll") for (int i = 0; i < NXMAX; ++i) rx[i] = xsrc[xoff[i]];                                 \
         _Pragma("unroll") for (int i = 0; i < 8; ++i) rd[i] = dsrc[doff[i]];                                     \
     }
 #define STEM_STAGE()                                                                                             \
     {                                                                                                            \
         _Pragma("unroll") for (int i = 0; i < NXMAX; ++i)                                                        \
-            if (xok[i]) reinterpret_cast<f4*>(xs)[tid + 256 * i] = rx[i];                                        \
-        _Pragma("unroll") for (int i = 0; i < 8; ++i) reinterpret_cast<f4*>(dys)[tid + 256 * i] = rd[i];         \
+            if (xok[i]) reinterpret_cast<f32x4*>(xs)[tid + 256 * i] = rx[i];                                     \
+        _Pragma("unroll") for (int i = 0; i < 8; ++i) reinterpret_cast<f32x4*>(dys)[tid + 256 * i] = rd[i];      \
     }
 
     f32x16 acc[NTW];

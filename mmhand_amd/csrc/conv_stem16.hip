@@ -20,15 +20,10 @@
 // lane stores four consecutive channels of a pixel (store4's layout).  72 KiB of LDS at 24 channels: two work-groups
 // per CU.
 #include <algorithm>
-#include "common.h"
+#include "device_prims.h"
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef const bf16x8 __attribute__((address_space(3))) * lds_frag_p;
-__device__ __forceinline__ bf16x8 lds_frag(unsigned addr) { return *reinterpret_cast<lds_frag_p>((size_t)addr); }
+using namespace mmh::dev;
 
 constexpr int TS = 16;                      // output tile 16 x 16
 
@@ -49,14 +44,6 @@ struct Stem16KP {
     float* stats;           // per (image, tile, wave, channel) count / mean / M2 of the stored outputs, [B][chunks][3][64], or null
 };
 
-template <bool H16>
-__device__ __forceinline__ f32x4 mfma16(bf16x8 a, bf16x8 b, f32x4 c) {
-    if (H16)
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0,
-                                                      0, 0);
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-
 // RW = output rows per wave: 4 (256 threads; two work-groups per CU where LDS allows) or 2 (512 threads: the 40-48 channel
 // stems, whose 144 KiB of LDS admit one work-group per CU - eight waves instead of four to hide the fragment reads)
 template <bool H16, int RW>
@@ -66,14 +53,13 @@ __global__ void __launch_bounds__(64 * (TS / RW), 2) conv_stem16_kernel(const St
     const int tid = threadIdx.x;
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l15 = lane & 15, g4 = lane >> 4;
-    const int per_xcd = (p.tiles + 7) / 8;
-    const int tile = (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
+    const int tile = xcd_item(p.tiles);
     if (tile >= p.tiles) return;
     const int b = tile / (p.TX * p.TY);
     const int trem = tile - b * (p.TX * p.TY);
     const int ty = trem / p.TX, tx = trem - ty * p.TX;
     const int oh0 = ty * TS, ow0 = tx * TS;
-    const unsigned lds0 = mmh::lds_addr_of(smem);
+    const unsigned lds0 = lds_addr_of(smem);
     const unsigned wdst = __builtin_amdgcn_readfirstlane(lds0 + (unsigned)wave * 1024u);
 
     // filter row kh -> weight stage kh & 1 (linear copy of the padded [64][wpitch] image)
@@ -83,7 +69,7 @@ __global__ void __launch_bounds__(64 * (TS / RW), 2) conv_stem16_kernel(const St
         const unsigned dst = wdst + (unsigned)p.halo_b + (unsigned)((kh & 1) * p.wst_b);
         for (int r = 0; r * NT < w_units; ++r) {
             const int u = r * NT + tid;
-            mmh::lds_dma16(u < w_units ? src + (size_t)u * 16 : p.zeros + (lane & 7) * 16, dst + (unsigned)(r * NT * 16));
+            lds_dma16(u < w_units ? src + (size_t)u * 16 : p.zeros + (lane & 7) * 16, dst + (unsigned)(r * NT * 16));
         }
     };
     // halo: unit u of the flat image (22 rows x upr units): row u / upr, pixel (u % upr) / c8u, chunk (u % upr) % c8u;
@@ -104,7 +90,7 @@ __global__ void __launch_bounds__(64 * (TS / RW), 2) conv_stem16_kernel(const St
             const bool ok = u < units && ih >= 0 && ih < p.H && iw >= 0 && iw < p.W;
             const char* g = ok ? p.x + (size_t)((b * p.H + ih) * p.W + iw) * (size_t)(p.C8 * 2) + (unsigned)ck * 16u
                                : p.zeros + (lane & 7) * 16;
-            mmh::lds_dma16(g, wdst + (unsigned)(r * NT * 16));
+            lds_dma16(g, wdst + (unsigned)(r * NT * 16));
         }
     }
     issue_w(0);
@@ -135,7 +121,7 @@ __global__ void __launch_bounds__(64 * (TS / RW), 2) conv_stem16_kernel(const St
 #pragma unroll
             for (int i = 0; i < RW; ++i)
 #pragma unroll
-                for (int j = 0; j < 4; ++j) acc[i][j] = mfma16<H16>(wf[j], xf[i], acc[i][j]);
+                for (int j = 0; j < 4; ++j) acc[i][j] = mfma_16x16x32<H16>(wf[j], xf[i], acc[i][j]);
         }
     }
 
@@ -145,7 +131,7 @@ __global__ void __launch_bounds__(64 * (TS / RW), 2) conv_stem16_kernel(const St
 #pragma unroll
         for (int r = 0; r < 4; ++r) bv[j][r] = p.bias ? p.bias[j * 16 + 4 * g4 + r] : 0.f;
     const int ow = ow0 + l15;
-    // (16-byte stores after the lane-pair trade of common.h's pair_swap8: 24 -> 64 396 us against 348 with 8-byte stores - off)
+    // (16-byte stores after the lane-pair trade of pair_swap8: 24 -> 64 396 us against 348 with 8-byte stores - off)
     if (p.y16 && false) {
         const int cb0 = ((g4 & 1) ? 16 : 0) + 4 * (g4 & 2);
 #pragma unroll
@@ -155,13 +141,13 @@ __global__ void __launch_bounds__(64 * (TS / RW), 2) conv_stem16_kernel(const St
 #pragma unroll
             for (int jp = 0; jp < 2; ++jp) {
                 float v[8];
-                mmh::pair_swap8(acc[i][2 * jp], acc[i][2 * jp + 1], v);
+                pair_swap8(acc[i][2 * jp], acc[i][2 * jp + 1], v);
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
                     const float t = v[e] + (p.bias ? p.bias[jp * 32 + cb0 + e] : 0.f);
-                    v[e] = p.act == MMH_ACT_RELU ? (t > 0.f ? t : 0.f) : (p.act == MMH_ACT_TANH ? tanhf(t) : t);
+                    v[e] = act_apply(t, p.act);
                 }
-                if (oh < p.H && ow < p.W) mmh::store8_lp16<H16>(p.y16 + (m * p.y_cs + (jp * 32 + cb0)) * 2, v);
+                if (oh < p.H && ow < p.W) store8_lp16<H16>(p.y16 + (m * p.y_cs + (jp * 32 + cb0)) * 2, v);
             }
         }
     } else
@@ -171,33 +157,12 @@ __global__ void __launch_bounds__(64 * (TS / RW), 2) conv_stem16_kernel(const St
         if (oh >= p.H || ow >= p.W) continue;
         const size_t m = ((size_t)b * p.H + oh) * p.W + ow;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            f32x4 v = acc[i][j];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float t = v[r] + bv[j][r];
-                v[r] = p.act == MMH_ACT_RELU ? (t > 0.f ? t : 0.f) : (p.act == MMH_ACT_TANH ? tanhf(t) : t);
-            }
-            const size_t elem = m * p.y_cs + (j * 16 + 4 * g4);
-            if (p.y16) {
-                if (H16) {
-                    typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-                    h4 o = {(_Float16)v[0], (_Float16)v[1], (_Float16)v[2], (_Float16)v[3]};
-                    *reinterpret_cast<h4*>(p.y16 + elem * 2) = o;
-                } else {
-                    typedef __bf16 b4 __attribute__((ext_vector_type(4)));
-                    b4 o = {(__bf16)v[0], (__bf16)v[1], (__bf16)v[2], (__bf16)v[3]};
-                    *reinterpret_cast<b4*>(p.y16 + elem * 2) = o;
-                }
-            } else {
-                *reinterpret_cast<f32x4*>(p.y + elem) = v;
-            }
-        }
+        for (int j = 0; j < 4; ++j) store4<H16>(p.y, p.y16, m * p.y_cs + (j * 16 + 4 * g4), acc[i][j], bv[j], p.act);
     }
     if (p.stats) {      // full tiles, 16-bit output, no activation (host side): the norm behind the stem merges these partials
         constexpr int WPT = TS / RW;        // waves (= partials) per tile
         float* sp = p.stats + ((size_t)(b * (p.TX * p.TY * WPT) + (ty * p.TX + tx) * WPT + wave) * 3) * 64 + 4 * g4;
-        mmh::wave_tile_stats<RW, 4>([&](int i, int j, int r) {
+        wave_tile_stats<RW, 4>([&](int i, int j, int r) {
             const float t = acc[i][j][r] + bv[j][r];
             return H16 ? (float)(_Float16)t : (float)(__bf16)t;
         }, l15, sp, 64);

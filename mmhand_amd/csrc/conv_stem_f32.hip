@@ -20,18 +20,12 @@
 // 4 v_mfma_f32_32x32x2_f32.  Epilogue: bias, activation, and - for the norm layer behind the stem - the (count, mean, M2)
 // partials of each wave's 32 pixels per channel (mmh_conv2d_fprop_stats).  Persistent, XCD-contiguous tile lists.
 #include <algorithm>
-#include "common.h"
+#include "device_prims.h"
 
 namespace mmh { int g_stem_f32 = 1; int g_stem_f32_dbg = 0; int g_stem_f32_levels = 1; }   // levels 2: with mmh_set_option("conv_levels", 2)
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef const f32x4 __attribute__((address_space(3))) * lds_f4_p;
-typedef const float __attribute__((address_space(3))) * lds_f_p;
-__device__ __forceinline__ f32x4 lds_f4(unsigned addr, int imm) { return *reinterpret_cast<lds_f4_p>((size_t)(addr + (unsigned)imm)); }
-__device__ __forceinline__ float lds_f(unsigned addr, int imm) { return *reinterpret_cast<lds_f_p>((size_t)(addr + (unsigned)imm)); }
+using namespace mmh::dev;
 
 constexpr int NT = 512;
 constexpr int TC = 16, HC = TC + 6;             // output tile: 8 MT rows x 16 pixels; halo (8 MT + 6) x 22 pixels
@@ -57,12 +51,6 @@ struct StemF32KP {
     int TX, TY, tiles, per_xcd, slots, dbg;
 };
 
-__device__ __forceinline__ float act_of(float v, int act) {
-    if (act == MMH_ACT_RELU) return v > 0.f ? v : 0.f;
-    if (act == MMH_ACT_TANH) return tanhf(v);
-    return v;
-}
-
 // MT: 32-pixel accumulator tiles per wave: output tile 8 MT rows x 16 pixels (wave: rows 2 pg, 2 pg + 1 of each half of 8)
 // LEVELS = 2 (mmh_set_option("conv_levels", 2), the accuracy modes of ops.set_winograd_mode): two-level summation - every
 // filter phase (<= 160 of the 7 x 7 Cin contraction values) runs its own MFMA chain in `part`, folded into the totals by
@@ -75,7 +63,7 @@ __global__ void __launch_bounds__(NT, 1) conv_stem_f32_kernel(const StemF32KP p)
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int m = lane & 31, kg = lane >> 5;
     const int pg = wave & 3, nh = wave >> 2;
-    const unsigned lds0 = mmh::lds_addr_of(smem);
+    const unsigned lds0 = lds_addr_of(smem);
     const unsigned wdst = __builtin_amdgcn_readfirstlane(lds0 + (unsigned)wave * 1024u);
     const unsigned w_lds = (unsigned)(p.nhalo * p.halo_b);
     const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
@@ -95,7 +83,7 @@ __global__ void __launch_bounds__(NT, 1) conv_stem_f32_kernel(const StemF32KP p)
         const unsigned dst = wdst + w_lds + (unsigned)(st * p.wst_b);
         for (int rr = 0; rr < p.wrounds; ++rr) {
             const int u = rr * NT + tid;
-            mmh::lds_dma16((u >> 4) < rows ? (const void*)(src + u * 4) : zero, dst + (unsigned)(rr * NT * 16));
+            lds_dma16((u >> 4) < rows ? (const void*)(src + u * 4) : zero, dst + (unsigned)(rr * NT * 16));
         }
     };
     auto issue_halo = [&](int tile, int buf) {
@@ -116,7 +104,7 @@ __global__ void __launch_bounds__(NT, 1) conv_stem_f32_kernel(const StemF32KP p)
             }
             const bool ok = live && u < units && ih >= 0 && ih < p.H && iw >= 0 && iw < p.W;
             const void* g = ok ? (const void*)(p.x + ((size_t)(b * p.H + ih) * p.W + iw) * (size_t)p.x_cs + 4 * ck) : zero;
-            mmh::lds_dma16(g, wdst + (unsigned)(buf * p.halo_b) + (unsigned)(rr * NT * 16));
+            lds_dma16(g, wdst + (unsigned)(buf * p.halo_b) + (unsigned)(rr * NT * 16));
         }
     };
 
@@ -233,7 +221,7 @@ __global__ void __launch_bounds__(NT, 1) conv_stem_f32_kernel(const StemF32KP p)
                 const int mm = (i & 3) + 8 * (i >> 2) + 4 * kg;
                 const int oh = ty * TR + 8 * mt + 2 * pg + (mm >> 4), ow = tx * TC + (mm & 15);
                 if (oh < p.H && ow < p.W)
-                    p.y[((size_t)(b * p.H + oh) * p.W + ow) * (size_t)p.y_cs + n] = act_of(acc[mt][i] + bv, p.act);
+                    p.y[((size_t)(b * p.H + oh) * p.W + ow) * (size_t)p.y_cs + n] = act_apply(acc[mt][i] + bv, p.act);
             }
         }
         if (p.stats) {

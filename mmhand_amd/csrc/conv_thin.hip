@@ -18,9 +18,10 @@
 // flipped, transposed filter and pad 6 (full correlation) into the padded domain, then the
 // reflect fold (mmh_reflect_fold's kernel) when the forward conv was reflect padded.
 #include <algorithm>
-#include "common.h"
+#include "device_prims.h"
 
 namespace {
+using namespace mmh::dev;
 
 constexpr int TW = 64, TH = 16;         // output tile: 64 columns (lanes) x 16 rows (4 waves x 4 rows)
 constexpr int HC = TW + 6, HR = TH + 6; // staged input tile incl. the 7x7 halo
@@ -41,12 +42,6 @@ struct ThinKP {
     int tiles_x, tiles_y;
     int x_lp;                   // element type of x: 0 fp32, 1 bf16, 2 fp16 (x_bytes in that type)
 };
-
-__device__ __forceinline__ float thin_act(float v, int act) {
-    if (act == MMH_ACT_RELU) return v > 0.f ? v : 0.f;
-    if (act == MMH_ACT_TANH) return tanhf(v);
-    return v;
-}
 
 __global__ void __launch_bounds__(256) thin_conv7_kernel(const ThinKP p) {
     __shared__ float4 xs[HR * HC];
@@ -150,10 +145,10 @@ __global__ void __launch_bounds__(256) thin_conv7_kernel(const ThinKP p) {
         const int oh = oh0 + wave * 4 + q;
         if (oh < p.Ho && ow < p.Wo) {
             float4 o;
-            o.x = thin_act(acc[q][0].x + bs[0], p.act);
-            o.y = thin_act(acc[q][0].y + bs[1], p.act);
-            o.z = thin_act(acc[q][1].x + bs[2], p.act);
-            o.w = thin_act(acc[q][1].y + bs[3], p.act);
+            o.x = act_apply(acc[q][0].x + bs[0], p.act);
+            o.y = act_apply(acc[q][0].y + bs[1], p.act);
+            o.z = act_apply(acc[q][1].x + bs[2], p.act);
+            o.w = act_apply(acc[q][1].y + bs[3], p.act);
             *reinterpret_cast<float4*>(p.y + ((size_t)(b * p.Ho + oh) * p.Wo + ow) * p.y_cs) = o;
         }
     }

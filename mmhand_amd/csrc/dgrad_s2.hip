@@ -26,16 +26,12 @@
 // summation per class).  Ablations (tools/ablate_dgrad_s2.py): no DMA, no stores 545 us = 142 TFLOP/s.
 #include <algorithm>
 #include <type_traits>
-#include "common.h"
+#include "device_prims.h"
 
 namespace mmh { int g_dgrad_s2_halo = 1; int g_dgrad_s2_dbg = 0; }
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef const f32x4 __attribute__((address_space(3))) * lds_f4_p;
-__device__ __forceinline__ f32x4 lds_f4(unsigned addr) { return *reinterpret_cast<lds_f4_p>((size_t)addr); }
+using namespace mmh::dev;
 
 constexpr int KC = 64;                          // channels of one chunk of the contraction
 constexpr int TH = 8, TW = 16;                  // dy positions per tile
@@ -49,10 +45,6 @@ constexpr int HALO_B = HROUNDS * PPR * PIXB;    // 40960 per chunk
 constexpr int lds_bytes(int ntn) { return 2 * HALO_B + 2 * (64 * ntn) * PIXB; }      // 114688 / 147456
 
 __device__ char g_zero_line[128];               // DMA source of the zero padding
-// LDS-DMA with a scalar base and a 32-bit lane offset (mmh::lds_dma16 takes a 64-bit pointer per lane)
-__device__ __forceinline__ void dma16_s(const void* sbase, unsigned voff, unsigned lds_base) {
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(sbase), "s"(lds_base) : "memory", "m0");
-}
 // s_waitcnt vmcnt(n) lgkmcnt(0) (gfx9 encoding: vmcnt in bits 3:0 and 15:14, expcnt 6:4 left at 7)
 constexpr int wait_vm(int n) { return (n & 15) | ((n >> 4) << 14) | 0x0070; }
 template <int V> using IC = std::integral_constant<int, V>;
@@ -104,7 +96,7 @@ __global__ void __launch_bounds__(NT, 1) dgrad_s2_kernel(const DgradS2KP p) {
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r = lane & 31, kg = lane >> 5;
     const int pg = wave & 3, ch = wave >> 2;
-    const unsigned lds0 = mmh::lds_addr_of(smem);
+    const unsigned lds0 = lds_addr_of(smem);
     const unsigned wdst = __builtin_amdgcn_readfirstlane(lds0 + (unsigned)wave * 1024u);
     const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
     const int t_end = min(p.tiles, (xcd + 1) * p.per_xcd);
@@ -144,7 +136,7 @@ __global__ void __launch_bounds__(NT, 1) dgrad_s2_kernel(const DgradS2KP p) {
         for (int rr = 0; rr < HROUNDS; ++rr) {
             const bool ok = (int)(h_yx[rr] & 0xff) < ph_room && (int)(h_yx[rr] >> 8) < pw_room;
             const void* g = ok ? (const void*)(src + h_off[rr]) : (const void*)(g_zero_line + (lane & 7) * 16);
-            mmh::lds_dma16(g, wdst + (unsigned)((kq & 1) * HALO_B) + (unsigned)(rr * NT * 16));
+            lds_dma16(g, wdst + (unsigned)((kq & 1) * HALO_B) + (unsigned)(rr * NT * 16));
         }
     };
 

@@ -6,7 +6,7 @@
 // reproducible run to run.
 #include <algorithm>
 #include <cmath>
-#include "common.h"
+#include "device_prims.h"
 
 namespace mmh { int g_pw_v2 = 1; int g_col_chunks = 2048; int g_row_chunks = 4096; }
 // mmh_set_dropout_salt: a device uint64 that every dropout-drawing kernel adds to its by-value seed when it runs (NULL = none).
@@ -15,6 +15,7 @@ namespace mmh { int g_pw_v2 = 1; int g_col_chunks = 2048; int g_row_chunks = 409
 static const uint64_t* g_dropout_salt = nullptr;   // mmh_set_option("pw_v2"): 0 = first-generation pointwise kernels (A/B)
 
 namespace {
+using namespace mmh::dev;
 
 constexpr int TPB = 256;
 
@@ -795,10 +796,10 @@ __global__ void __launch_bounds__(TPB) norm_bwd_apply_v2(
                 // dx = k0*(dz - s1/count) - xhat*k0*s2/count, xhat = (x-mu)*invstd
                 if (RC) {
                     const bool keep = ((kb[u] >> e) & 1u) && (!relu || __builtin_fmaf(xv.v[e], sc.v[e], sf.v[e]) > 0.f);
-                    o.v[e] = mmh::norm_bwd_elem(gv.v[e], keep, dsc, xv.v[e], mu.v[e], k0[e], k1[e], k2[e]);
+                    o.v[e] = norm_bwd_elem(gv.v[e], keep, dsc, xv.v[e], mu.v[e], k0[e], k1[e], k2[e]);
                 } else {
                     const bool keep = !masked || ((kb[u] >> (e < 4 ? e : e + 4)) & 1u);
-                    o.v[e] = mmh::norm_bwd_elem(gv.v[e], keep, masked ? dsc : 1.f, xv.v[e], mu.v[e], k0[e], k1[e], k2[e]);
+                    o.v[e] = norm_bwd_elem(gv.v[e], keep, masked ? dsc : 1.f, xv.v[e], mu.v[e], k0[e], k1[e], k2[e]);
                 }
             }
             st8<DW>(dx, (gbase + rr) * rg.c8 + q, o, dh16);
@@ -818,7 +819,7 @@ __global__ void __launch_bounds__(TPB) norm_bwd_apply_v2(
 // kernels' terms (dz = keep ? g * dsc : 0; xhat = (x - mu) * invstd) in a different, fixed order (64-lane butterflies, then
 // the 16 waves in order); the apply is the same expression regrouped around three coefficients.  Deterministic; equal to the
 // two-pass result to rounding, not bit for bit.
-// exactly the two-pass kernels' (dz = keep ? g * dsc : 0; mmh::norm_bwd_elem); only the ORDER of the plane sums differs
+// exactly the two-pass kernels' (dz = keep ? g * dsc : 0; norm_bwd_elem); only the ORDER of the plane sums differs
 // (64-lane butterflies, then the 16 waves in order): deterministic, not bit-identical to the two-pass sums.
 constexpr int FT = 1024;
 // H16: the 16-bit tensors are IEEE fp16 (else bf16); MASKED: keep bits present - template parameters (run-time branches
@@ -935,13 +936,13 @@ __global__ void __launch_bounds__(FT) norm_bwd_plane_kernel(
     char* dp = static_cast<char*>(dx) + gb8 * (DW ? 16 : 32);
     // x: global -> LDS by DMA, one 16-byte unit per lane and row, unit (u, tid) at plane_x + 16 (u FT + tid): every lane
     // reads back exactly what its own DMA brought, so its own vmcnt wait is all the ordering there is (no barrier)
-    const unsigned xl = mmh::lds_addr_of(plane_x) + (unsigned)__builtin_amdgcn_readfirstlane(tid & ~63) * 16u;
+    const unsigned xl = lds_addr_of(plane_x) + (unsigned)__builtin_amdgcn_readfirstlane(tid & ~63) * 16u;
     const unsigned unit0 = (unsigned)(rs * c8 + cq), ustride = (unsigned)(nslots * c8);
     const bool tail = (NR - 1) * nslots + rs >= rows;       // some of this lane's rows lie past the plane
 #pragma unroll
     for (int u = 0; u < NR; ++u) {
         const unsigned unit = tail ? (unsigned)(min(rs + u * nslots, rows - 1) * c8 + cq) : unit0 + (unsigned)u * ustride;
-        mmh::lds_dma16(xp + (size_t)unit * 16, xl + (unsigned)u * (FT * 16u));
+        lds_dma16(xp + (size_t)unit * 16, xl + (unsigned)u * (FT * 16u));
     }
     PlaneBody<GW, DW, NR, H16, MASKED> pb;
     pb.rs = rs; pb.nslots = nslots; pb.rows = rows;

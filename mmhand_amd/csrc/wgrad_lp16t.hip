@@ -28,21 +28,16 @@
 // Pipeline: ring of four 32-KiB stages; a stage is issued three blocks ahead and waited for (vmcnt(4): every wave
 // issues exactly four loads per stage, also past the end of its range, where they read the zero page) one k16-step
 // before its first use, at the one barrier per block.  Fragments: the three A fragments of the next filter row are
-// requested while the current row's three MFMAs (32x32x16) run.  The LDS-DMA is issued as inline asm (mmh::lds_dma16:
+// requested while the current row's three MFMAs (32x32x16) run.  The LDS-DMA is issued as inline asm (lds_dma16:
 // hipcc would otherwise drain the ring behind every issue).
 //
 // Split-K over block ranges (one round of workgroups, split-major work list so that the tiles of one split sit on
 // one XCD and share its L2), fp32 slabs [split][tap][Cin][Cout], fixed-order reduction (lp16_slab_reduce_kernel).
 #include <algorithm>
-#include "common.h"
+#include "device_prims.h"
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void* lds_vp;
+using namespace mmh::dev;
 
 constexpr int TCI = 64, TCO = 128;          // tile: input channels x output channels (x 9 taps)
 constexpr int BC = 16;                      // pixel block columns = one k16-step
@@ -85,14 +80,6 @@ struct LpWgradTP {
     int CT, NT, S, items;
 };
 
-template <bool H16>
-__device__ __forceinline__ f32x16 mfma32(bf16x8 a, bf16x8 b, f32x16 c) {
-    if (H16)
-        return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0,
-                                                      0, 0);
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
-
 // 8 consecutive k rows (k = 8 h .. 8 h + 7 of the k16-step) of one column per lane: two transposed reads 4 rows apart
 template <int ROWBYTES>
 __device__ __forceinline__ bf16x8 tr_frag(const char* a) {
@@ -113,8 +100,7 @@ __global__ void __launch_bounds__(512, 2) wgrad_lp16t_kernel(const LpWgradTP p) 
     const int l31 = lane & 31, h = lane >> 5;
     const int wr = wave >> 2, wc = wave & 3;
     const bool stagger = p.stagger != 0;
-    const int per_xcd = (p.items + 7) / 8;
-    int item = (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
+    int item = xcd_item(p.items);
     if (item >= p.items) return;
     const int nt = item % p.NT; item /= p.NT;
     const int ct = item % p.CT;
@@ -153,7 +139,7 @@ __global__ void __launch_bounds__(512, 2) wgrad_lp16t_kernel(const LpWgradTP p) 
     int nb_tr = (nb - nb_img * p.TR * p.TC) / p.TC;
     int nb_tc = nb - (nb_img * p.TR + nb_tr) * p.TC;
     int slot_next = 0;
-    const unsigned lds0 = mmh::lds_addr_of(smem);
+    const unsigned lds0 = lds_addr_of(smem);
     const unsigned xdst = __builtin_amdgcn_readfirstlane(lds0 + (unsigned)wave * 1024u);                   // + 8 KiB per j
     const unsigned ddst = __builtin_amdgcn_readfirstlane(lds0 + XSTAGE + (unsigned)(DJ * wave) * 1024u);   // + 1 KiB per j
     auto issue = [&]() {
@@ -173,7 +159,7 @@ __global__ void __launch_bounds__(512, 2) wgrad_lp16t_kernel(const LpWgradTP p) 
             const bool ok = live && x_row[j] && ih >= 0 && ih < p.H && iw >= 0 && iw < p.W;
             const char* g = ok ? p.x + (size_t)((nb_img * p.H + ih) * p.W + iw) * (size_t)(p.x_cs * 2) + x_coff[j]
                                : p.zeros + (lane & 7) * 16;
-            mmh::lds_dma16(g, xdst + sbase + (unsigned)j * 8192u);
+            lds_dma16(g, xdst + sbase + (unsigned)j * 8192u);
         }
 #pragma unroll
         for (int j = 0; j < DJ; ++j) {
@@ -181,7 +167,7 @@ __global__ void __launch_bounds__(512, 2) wgrad_lp16t_kernel(const LpWgradTP p) 
             const bool ok = live && oh < p.Ho && ow < p.Wo;
             const char* g = ok ? p.dy + (size_t)((nb_img * p.Ho + oh) * p.Wo + ow) * (size_t)(p.dy_cs * 2) + d_coff[j]
                                : p.zeros + (lane & 15) * 16;
-            mmh::lds_dma16(g, ddst + sbase + (unsigned)j * 1024u);
+            lds_dma16(g, ddst + sbase + (unsigned)j * 1024u);
         }
         ++nb;
         if (++nb_tc == p.TC) {
@@ -266,7 +252,7 @@ __global__ void __launch_bounds__(512, 2) wgrad_lp16t_kernel(const LpWgradTP p) 
                     }
 #pragma unroll
                     for (int kw = 0; kw < 3; ++kw)
-                        acc[kh * 3 + kw] = mfma32<H16>(af[cur][kw], bfr[kk & 1], acc[kh * 3 + kw]);
+                        acc[kh * 3 + kw] = mfma_32x32x16<H16>(af[cur][kw], bfr[kk & 1], acc[kh * 3 + kw]);
                 }
             }
             slot = slot_n;

@@ -15,15 +15,12 @@
 // one barrier per row.  Each work-group writes its block of dw once, into its slab; a fixed-order reduction sums the slabs
 // (slab_reduce.hip).
 #include <algorithm>
-#include "common.h"
+#include "device_prims.h"
 
 namespace mmh { int g_wgrad_s2_strip = 1; }
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef const float __attribute__((address_space(3))) * lds_f_p;
-__device__ __forceinline__ float lds_f(unsigned addr, int imm) { return *reinterpret_cast<lds_f_p>((size_t)(addr + (unsigned)imm)); }
+using namespace mmh::dev;
 
 constexpr int NT = 512;
 constexpr int SW = 16;                          // dy positions per strip row
@@ -52,7 +49,7 @@ __global__ void __launch_bounds__(NT, 1) wgrad_s2_kernel(const WgradS2KP p) {
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int m = lane & 31, k = lane >> 5;
     const int ct = wave >> 2, nt = wave & 3;
-    const unsigned lds0 = mmh::lds_addr_of(smem);
+    const unsigned lds0 = lds_addr_of(smem);
     const unsigned wdst = __builtin_amdgcn_readfirstlane(lds0 + (unsigned)wave * 1024u);
 
     // XCD x works on a contiguous range of units; the channel blocks of one (image, strip, rows) unit are neighbours
@@ -99,7 +96,7 @@ __global__ void __launch_bounds__(NT, 1) wgrad_s2_kernel(const WgradS2KP p) {
             const void* g = zero;
             if (d_kind[rr] == 0 && okx) g = xb + d_off[rr];
             if (d_kind[rr] == 1 && okd) g = db + d_off[rr];
-            mmh::lds_dma16(g, dst + (unsigned)(rr * NT * 16));
+            lds_dma16(g, dst + (unsigned)(rr * NT * 16));
         }
     };
 

@@ -23,14 +23,10 @@
 // C8 = 48 (7 x 11 pairs) takes two work-group kinds (filter rows 0-3 / 4-6).  fp32 slabs [split][7][JP][64] are summed
 // in a fixed order into dw by stem_slab_reduce_kernel (deterministic).
 #include <algorithm>
-#include "common.h"
+#include "device_prims.h"
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
+using namespace mmh::dev;
 
 constexpr int BR = 4, BC = 16;              // pixel block: 4 rows x 16 columns
 constexpr int HR = BR + 6, HC = BC + 6;     // halo 10 x 22 pixels
@@ -52,14 +48,6 @@ struct StemWgKP {
     int xstage, tstage;     // x bytes per stage (rounded up to the DMA rounds' footprint), stage bytes
 };
 
-template <bool H16>
-__device__ __forceinline__ f32x16 mfma32(bf16x8 a, bf16x8 b, f32x16 c) {
-    if (H16)
-        return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0,
-                                                      0, 0);
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
-
 // 8 consecutive k rows of one column per lane: two transposed reads 4 rows apart (rows `rowbytes` apart)
 __device__ __forceinline__ bf16x8 tr_frag(unsigned addr, unsigned rowbytes) {
     typedef s16x4 __attribute__((address_space(3))) * lds_p;
@@ -75,8 +63,7 @@ __global__ void __launch_bounds__(512, 2) wgrad_stem_kernel(const StemWgKP p) {
     const int tid = threadIdx.x;
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l31 = lane & 31, h = lane >> 5;
-    const int per_xcd = (p.S * p.KG + 7) / 8;
-    const int item = (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
+    const int item = xcd_item(p.S * p.KG);
     if (item >= p.S * p.KG) return;
     const int kg = item % p.KG, split = item / p.KG;
     const int kh_lo = kg == 0 ? 0 : 4, nkh = p.KG == 1 ? 7 : (kg == 0 ? 4 : 3);
@@ -104,7 +91,7 @@ __global__ void __launch_bounds__(512, 2) wgrad_stem_kernel(const StemWgKP p) {
     int nb_tr = (nb - nb_img * p.TR * p.TC) / p.TC;
     int nb_tc = nb - (nb_img * p.TR + nb_tr) * p.TC;
     int slot_next = 0;
-    const unsigned lds0 = mmh::lds_addr_of(smem);
+    const unsigned lds0 = lds_addr_of(smem);
     const unsigned wdst = __builtin_amdgcn_readfirstlane(lds0 + (unsigned)wave * 1024u);
     auto issue = [&]() {
         const unsigned sbase = (unsigned)slot_next * (unsigned)p.tstage;
@@ -123,7 +110,7 @@ __global__ void __launch_bounds__(512, 2) wgrad_stem_kernel(const StemWgKP p) {
             const bool ok = live && x_hy[r] >= 0 && ih >= 0 && ih < p.H && iw >= 0 && iw < p.W;
             const char* g = ok ? p.x + (size_t)((nb_img * p.H + ih) * p.W + iw) * (size_t)(p.C8 * 2) + x_ck[r]
                                : p.zeros + (lane & 7) * 16;
-            mmh::lds_dma16(g, wdst + sbase + (unsigned)r * 8192u);
+            lds_dma16(g, wdst + sbase + (unsigned)r * 8192u);
         }
         {
             const int oh = r0 + d_py, ow = c0 + d_px;
@@ -137,7 +124,7 @@ __global__ void __launch_bounds__(512, 2) wgrad_stem_kernel(const StemWgKP p) {
             }
             const char* g = ok ? p.dy + (size_t)((nb_img * p.dyH + sh) * p.dyW + sw) * (size_t)(p.dy_cs * 2) + d_ck
                                : p.zeros + (lane & 7) * 16;
-            mmh::lds_dma16(g, wdst + sbase + (unsigned)p.xstage);
+            lds_dma16(g, wdst + sbase + (unsigned)p.xstage);
         }
         ++nb;
         if (++nb_tc == p.TC) {
@@ -194,8 +181,8 @@ __global__ void __launch_bounds__(512, 2) wgrad_stem_kernel(const StemWgKP p) {
                 for (int i = 0; i < PW; ++i) {
                     if (wave + 8 * i < npairs) {
                         const bf16x8 af = tr_frag(a_lane + sb + a_off[i] + (unsigned)(kk * p.rp), xrow);
-                        acc[i][0] = mfma32<H16>(af, b0, acc[i][0]);
-                        acc[i][1] = mfma32<H16>(af, b1, acc[i][1]);
+                        acc[i][0] = mfma_32x32x16<H16>(af, b0, acc[i][0]);
+                        acc[i][1] = mfma_32x32x16<H16>(af, b1, acc[i][1]);
                     }
                 }
             }

@@ -14,20 +14,16 @@
 //   Yh [64][tiles][C]  = A dY A^T             wino6_dy        (wgrad)
 //   dw [3][3][Cin][Cout] = G^T dU G           wino6_dw
 // One thread per (tile, 2 channels), like the F(4x4,3x3) kernels in conv_igemm.hip.
-#include "common.h"
+#include "device_prims.h"
 
 namespace {
+using namespace mmh::dev;
+using mmh::dev::act_apply;     // beside the F2 overload below
 
 struct F2 { float x, y; };
 __device__ __forceinline__ F2 operator+(F2 a, F2 b) { return {a.x + b.x, a.y + b.y}; }
 __device__ __forceinline__ F2 operator-(F2 a, F2 b) { return {a.x - b.x, a.y - b.y}; }
 __device__ __forceinline__ F2 operator*(float k, F2 a) { return {k * a.x, k * a.y}; }
-
-__device__ __forceinline__ float act6(float v, int act) {
-    if (act == MMH_ACT_RELU) return v > 0.f ? v : 0.f;
-    if (act == MMH_ACT_TANH) return tanhf(v);
-    return v;
-}
 
 // out[0..7] = B^T in[0..7]
 template <typename T>
@@ -140,8 +136,7 @@ __global__ void __launch_bounds__(256) wino6_weights_multi_kernel(const long lon
 
 __device__ __forceinline__ float zero_of(float) { return 0.f; }
 __device__ __forceinline__ F2 zero_of(F2) { return F2{0.f, 0.f}; }
-__device__ __forceinline__ float act_of(float v, int act) { return act6(v, act); }
-__device__ __forceinline__ F2 act_of(F2 v, int act) { return F2{act6(v.x, act), act6(v.y, act)}; }
+__device__ __forceinline__ F2 act_apply(F2 v, int act) { return F2{act_apply(v.x, act), act_apply(v.y, act)}; }
 
 // T = F2: one thread per (tile, 2 channels); T = float: per (tile, channel) - half the registers,
 // twice the waves per SIMD (C2 is the channel count in units of T)
@@ -402,7 +397,7 @@ __global__ void __launch_bounds__(256) wino6_output_kernel(const float* __restri
 #pragma unroll
         for (int q = 0; q < 6; ++q) {
             const int ww = 6 * tx + q;
-            vals[r][q] = act_of(o6[q] + bv, act);
+            vals[r][q] = act_apply(o6[q] + bv, act);
             if (hh < H && ww < W) {
                 yo[(((long long)b * H + hh) * W + ww) * C2 + c] = vals[r][q];
                 stat_add(vals[r][q], n, sum);
@@ -536,7 +531,7 @@ __global__ void __launch_bounds__(256) wino6_input_dy_kernel(const float* __rest
 
 // Norm backward inside the transform: dy is not read but computed per element from the gradient g of the
 // norm's OUTPUT, the norm's input x and the per-(group, channel) sums of mmh_norm_bwd_reduce_rc - the
-// arithmetic of norm_bwd_apply_v2<.., RC> (pointwise.hip; mmh::norm_bwd_elem) - so the gradient of the conv
+// arithmetic of norm_bwd_apply_v2<.., RC> (pointwise.hip; norm_bwd_elem) - so the gradient of the conv
 // output between that conv and its norm is never written to HBM.  Loads first, arithmetic after, as in
 // wino6_input_normact_kernel; x is staged four rows at a time (96 instead of 128 live window registers).
 struct NormBwdPro {
@@ -614,7 +609,7 @@ __global__ void __launch_bounds__(256, 4) wino6_input_dy_normbwd_kernel(const fl
                     const uint32_t wsel = (wg.ww[q] >> 5) == wq0 ? lo[r] : hi[r];
                     keep = keep && ((wsel >> (wg.ww[q] & 31)) & 1u);
                 }
-                const float o = mmh::norm_bwd_elem(d[rr][q], keep, nb.np.dsc, xw[r][q], mu, k0, k1, k2);
+                const float o = norm_bwd_elem(d[rr][q], keep, nb.np.dsc, xw[r][q], mu, k0, k1, k2);
                 d[rr][q] = (wg.okh[rr] && wg.okw[q]) ? o : 0.f;
             }
         __builtin_amdgcn_sched_barrier(0);

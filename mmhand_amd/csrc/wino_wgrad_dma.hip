@@ -12,15 +12,12 @@
 // whole contraction - no split-K, no slab pass; fewer blocks than CUs (256 x 256: 64) split the tile range and sum slabs in a
 // fixed order (slab_reduce.hip).
 #include <algorithm>
-#include "common.h"
+#include "device_prims.h"
 
 namespace mmh { int g_wino_wgrad_dma = 1; }
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef const float __attribute__((address_space(3))) * lds_f_p;
-__device__ __forceinline__ float lds_f(unsigned addr, int imm) { return *reinterpret_cast<lds_f_p>((size_t)(addr + (unsigned)imm)); }
+using namespace mmh::dev;
 
 constexpr int NT = 512;
 constexpr int BMC = 256, BNC = 256;             // block: input channels x output channels
@@ -33,10 +30,6 @@ constexpr int LDS_B = NST * ST_B;               // 131072
 constexpr int AR = A_B / (NT * 16), BR = B_B / (NT * 16);      // 4 + 4 DMA instructions per thread and stage
 
 __device__ char g_zero_line[128];
-
-__device__ __forceinline__ void dma16_s(const void* sbase, unsigned voff, unsigned lds_base) {
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(sbase), "s"(lds_base) : "memory", "m0");
-}
 
 struct WinoWgradDmaKP {
     const float* V;         // [P][T][Cin]
@@ -53,7 +46,7 @@ __global__ void __launch_bounds__(NT, 1) wino_wgrad_dma_kernel(const WinoWgradDm
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int m = lane & 31, kk = lane >> 5;
     const int wm = wave >> 2, wn = wave & 3;
-    const unsigned lds0 = mmh::lds_addr_of(smem);
+    const unsigned lds0 = lds_addr_of(smem);
     const unsigned wdst = __builtin_amdgcn_readfirstlane(lds0 + (unsigned)wave * 1024u);
 
     // XCD x works on a contiguous range; the blocks of one (plane, split) read the same two panels
@@ -96,13 +89,13 @@ __global__ void __launch_bounds__(NT, 1) wino_wgrad_dma_kernel(const WinoWgradDm
 #pragma unroll
             for (int r = 0; r < AR; ++r) {
                 const int u = r * NT + tid;
-                mmh::lds_dma16((u >> 6) < rows ? (const void*)((const char*)(Vp + (size_t)row0 * p.Cin) + a_off[r]) : zero,
+                lds_dma16((u >> 6) < rows ? (const void*)((const char*)(Vp + (size_t)row0 * p.Cin) + a_off[r]) : zero,
                                dst + (unsigned)(r * NT * 16));
             }
 #pragma unroll
             for (int r = 0; r < BR; ++r) {
                 const int u = r * NT + tid;
-                mmh::lds_dma16((u >> 6) < rows ? (const void*)((const char*)(Yp + (size_t)row0 * p.Cout) + b_off[r]) : zero,
+                lds_dma16((u >> 6) < rows ? (const void*)((const char*)(Yp + (size_t)row0 * p.Cout) + b_off[r]) : zero,
                                dst + (unsigned)(A_B + r * NT * 16));
             }
         }

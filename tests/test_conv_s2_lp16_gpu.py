@@ -77,7 +77,7 @@ def test_stride2_fprop_kernel_declines_other_shapes(dev):
 @pytest.mark.parametrize("lp", [True, 2], ids=["bf16", "fp16"])
 def test_epilogue_statistics_match_the_stored_output(kind, B, H, W, Cin, lp, dev):
     """The partial statistics the stride-2 kernel (conv_s2_lp16.hip) and the 7x7 stem kernel (conv_stem16.hip) leave for the
-    InstanceNorm behind them (common.h: wave_tile_stats; mmh_conv_lp16_fprop_stats / mmh_conv_stem16_stats), merged by
+    InstanceNorm behind them (device_prims.h: wave_tile_stats; mmh_conv_lp16_fprop_stats / mmh_conv_stem16_stats), merged by
     mmh_norm_stats_merge: mean and M2 per (image, channel) of the 16-bit output AS STORED, against float64 over that output."""
     from mmhand_amd import lib as L
     from mmhand_amd import ops
