@@ -964,6 +964,32 @@ int mmh_png_encode_batch(const void* pixels /* uint8 [N][H][W][3] */, int N, int
                          void* streams /* N slots */, int64_t slot_bytes, int64_t* lengths /* [N] */, int32_t* status /* [N] */,
                          mmh_stream_t s);
 
+/* ---- pose distance and exact nearest-pose search (nearest_neighbor_search/nearest_neighbor_search.py:68-83, poseDistance) ----
+ * d(u, v) = arccos(clamp(f(u) . f(v), -1, 1)) / pi, f = the reference's identity(): the 20 consecutive joint differences of a
+ * [21][3] pose, flattened to 60 values, divided by their float64 2-norm.  The clamp is a stated divergence: the reference
+ * returns NaN where rounding puts the cosine above 1 (identical poses).  The reference searches with a pure-Python k-d tree
+ * over other features, which is not exact under this distance; here the search is all pairs on the fp64 MFMA with the
+ * selection in the epilogue - no Nq x Nc buffer, no atomics.
+ *
+ * mmh_pose_features (nearest_neighbor_search.py:68-83, identity()): C float64 [N][21][3] -> F float64 [N][64] (60 values +
+ *   4 zeros), valid int32 [N]: 0 for a pose with a non-finite coordinate or a zero norm, whose feature row is zero.
+ * mmh_pose_knn (nearest_neighbor_search.py:68-83 under the k-d tree's search_knn): for every query the k (1 .. 16) nearest
+ *   candidates, ranked by (larger cosine, then smaller candidate index) - a total order, and every cosine is one fixed chain
+ *   of MFMAs, so idx and dist are bit-identical for any cand_split.  Invalid candidates and exclude[q] (int32 [Nq] or NULL;
+ *   -1 = none) are never returned; an invalid query, or fewer valid candidates than k, leaves the trailing slots at
+ *   idx = -1, dist = NaN.  cand_split: candidates per slice (a multiple of 16), 0 = automatic (at most 32 slices); the
+ *   slices' lists are merged by a second kernel in slice order.  ws: mmh_pose_knn_ws_bytes(Nq, Nc, k, cand_split) bytes
+ *   (slices * Nq * k * 12, rounded up to 256; 0 = the arguments are refused), 8-byte aligned; F 16-byte aligned.
+ * mmh_pose_pair_distance (nearest_neighbor_search.py:68-83): d[i] of the pairs (Fa[i], Fb[i]), NaN if either is invalid.
+ * Bad arguments (NULL, N < 1, k outside 1 .. 16, cand_split not a multiple of 16) return non-zero before any launch.           */
+int mmh_pose_features(const double* C /* [N][21][3] */, int N, double* F /* [N][64] */, int32_t* valid /* [N] */, mmh_stream_t s);
+size_t mmh_pose_knn_ws_bytes(int Nq, int Nc, int k, int cand_split);          /* nearest_neighbor_search.py:68-83; host only */
+int mmh_pose_knn(const double* Fq, const int32_t* validq, int Nq, const double* Fc, const int32_t* validc, int Nc,
+                 const int32_t* exclude /* [Nq] or NULL */, int k, int cand_split, void* ws, int32_t* idx /* [Nq][k] */,
+                 double* dist /* [Nq][k] */, mmh_stream_t s);
+int mmh_pose_pair_distance(const double* Fa, const int32_t* valida, const double* Fb, const int32_t* validb, int n,
+                           double* d /* [n] */, mmh_stream_t s);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }

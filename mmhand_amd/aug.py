@@ -10,6 +10,9 @@ size the files hold - the resize is part of the device's decode pass - and the P
 bytes (row filters + Huffman-only DEFLATE in csrc/png_encode.hip), a pool of at most 16 threads writes them, and the next
 batch's forward is enqueued before the previous batch's bytes are fetched.  Same file names, same pixels, other bytes than
 PIL's.  MMH_DEVICE_PNG (the loader's switch for the input side) does not turn it on.
+`--pairing random|curriculum|nearest`, `--match_pool self|train` (additions, first form): how a target gets its source image
+(data.HandFolderLoader): `nearest` is the paper's inference with nearest-neighbour match - the source whose 3D pose is closest
+to the target's, out of the generation split itself or of the training share.  The file names do not change: one PNG per target.
 
 The first form reads the reference's prepared directory (data.HandFolderLoader: annotation.pickle + colour / depth PNGs,
 the generation side of the augmentation_ratio split, batch size 1, decoded on the device) and writes each generated image
@@ -28,7 +31,7 @@ import sys
 import numpy as np
 import torch
 
-from .data import HandFolderLoader, SyntheticHandLoader
+from .data import MATCH_POOLS, PAIRINGS, HandFolderLoader, SyntheticHandLoader
 from .inference import InferenceGenerator
 from .networks import Generator
 from .options import check_resize_inputs, default_train_opt
@@ -99,6 +102,14 @@ def main(argv, ngf=64, n_blocks=9, size=None, resize_inputs=0):
     if "--device_png" in argv:
         argv.remove("--device_png")
         device_png = True
+    pair_flags = {}
+    for flag, allowed in (("--pairing", PAIRINGS), ("--match_pool", MATCH_POOLS)):
+        if flag in argv:
+            i = argv.index(flag)
+            if i + 1 >= len(argv) or argv[i + 1] not in allowed:
+                raise ValueError(f"{flag}: expected one of {' | '.join(allowed)}")
+            pair_flags[flag[2:]] = argv[i + 1]
+            del argv[i:i + 2]
     ckp = argv[0]
     real = len(argv) == 6 and argv[3] in ("rhd", "stb")        # _, ckp, dataroot, DST, dataset, ratio, device = sys.argv
     if real:
@@ -107,6 +118,8 @@ def main(argv, ngf=64, n_blocks=9, size=None, resize_inputs=0):
     else:
         if device_png or batch_flag != 1:
             raise ValueError("--device_png / --batch belong to the prepared-directory form of the command line")
+        if pair_flags:
+            raise ValueError("--pairing / --match_pool belong to the prepared-directory form of the command line")
         dst = argv[1]
         n_batches = int(argv[2]) if len(argv) > 2 else 4
         batch = int(argv[3]) if len(argv) > 3 else 1
@@ -122,6 +135,8 @@ def main(argv, ngf=64, n_blocks=9, size=None, resize_inputs=0):
     if real:
         # aug.py:18-26: isTrain False, batchSize 1, not distributed; the loader hands decoded NCHW views
         opt.dataroot, opt.dataset, opt.augmentation_ratio, opt.distributed = dataroot, dataset, ratio, False
+        for name, value in pair_flags.items():
+            setattr(opt, name, value)
         loader = HandFolderLoader(opt, device=dev, decoded=True)
     else:
         loader = SyntheticHandLoader(opt, n_batches * batch, size=size)

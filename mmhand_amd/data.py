@@ -21,7 +21,11 @@ mmh_png_decode_batch (png.py) writes the same uint8 [B,H,W,3] BGR tensors.
 `HandFolderLoader(resident=True)` (--resident_dataset, MMH_RESIDENT_DATASET=1; off by default): the loader's order never
 changes between epochs, so the decoded images of this rank's batches are kept in device memory (uint8 [S,Hs,Ws,3], one slot
 per file).  The first epoch reads the files as above and copies each batch into the store (mmh_store_images); from then on a
-batch is a row of slots and ONE kernel (mmh_decode_inputs_indexed) - no file read, no PNG decode, no upload."""
+batch is a row of slots and ONE kernel (mmh_decode_inputs_indexed) - no file read, no PNG decode, no upload.
+
+`HandFolderLoader` with `opt.pairing` = curriculum | nearest (--pairing; the default `random` is the reference's live loader):
+the paper's two pairing strategies on the reference's pose distance (nearest_neighbor_search.py:68-83, on the device:
+ops.pose_features / pose_knn / pose_pair_distance).  Both are decided once, in the constructor, so the order stays static."""
 import os
 import pickle
 import random
@@ -169,6 +173,50 @@ def png_size(path):
     return int.from_bytes(head[20:24], "big"), int.from_bytes(head[16:20], "big")
 
 
+# ----------------------------------------------------------------------------- pose-distance pairing: host-side helpers
+PAIRINGS = ("random", "curriculum", "nearest")
+MATCH_POOLS = ("self", "train")
+
+
+def curriculum_order(dist):
+    """The curriculum's order of pairs: positions sorted by (pose distance, original position) - a stable ascending argsort,
+    pairs without a distance (NaN) last, among themselves in their original order.  Pure host code, no torch."""
+    d = np.asarray(dist, dtype=np.float64).reshape(-1)
+    nan = np.isnan(d)
+    return np.lexsort((np.arange(d.size), np.where(nan, 0.0, d), nan)).astype(np.int64)
+
+
+def apply_nearest(sources, pool, idx):
+    """-> (sources', fallbacks): the source of target i becomes pool[idx[i]] (idx: the nearest candidate of every target, [n]
+    or the [n, k] of ops.pose_knn, whose first column counts); where idx is -1 - no valid neighbour - the given source stays
+    and i is reported in `fallbacks`.  Pure host code, no torch."""
+    idx = np.asarray(idx)
+    if idx.ndim == 2:
+        idx = idx[:, 0]
+    if idx.shape != (len(sources),):
+        raise ValueError(f"apply_nearest: {len(sources)} sources, idx of shape {idx.shape}")
+    if ((idx < -1) | (idx >= len(pool))).any():
+        raise ValueError(f"apply_nearest: an index outside [-1, {len(pool)})")
+    out, fallbacks = list(sources), []
+    for i, j in enumerate(idx.tolist()):
+        if j < 0:
+            fallbacks.append(i)
+        else:
+            out[i] = pool[j]
+    return out, fallbacks
+
+
+def check_pairing(opt):
+    """(pairing, match_pool) of an options namespace, validated; absent attributes are the defaults (random, self)"""
+    pairing = getattr(opt, "pairing", None) or "random"
+    pool = getattr(opt, "match_pool", None) or "self"
+    if pairing not in PAIRINGS:
+        raise ValueError(f"--pairing {pairing!r}: expected one of {' | '.join(PAIRINGS)}")
+    if pool not in MATCH_POOLS:
+        raise ValueError(f"--match_pool {pool!r}: expected one of {' | '.join(MATCH_POOLS)}")
+    return pairing, pool
+
+
 class ResidentBatch:
     """One batch of a resident store: `idx` int32 [B,4] (a row block of the loader's device table) names the slots of
     (img1, img2, dep1, dep2) in `store` uint8 [S,Hs,Ws,3]; `uv_table` float64 [S,21,2] holds every slot's joints on the grid
@@ -234,8 +282,15 @@ class HandFolderLoader:
             raise NotImplementedError(f"--dataset {kind}: HandFolderLoader reads the prepared 'rhd' and 'stb' directories "
                                       "(the pair-list format of data/mmhand_dataset.py is not supported)")
         ratio = getattr(opt, "augmentation_ratio", None)
+        self.pairing, self.match_pool = check_pairing(opt)
         self.image_source, self.image_target = self._get_src_tgt(0.0 if ratio is None else float(ratio), data, key)
         self.device = device or torch.device("cuda", getattr(opt, "local_rank", 0) or 0)
+        # --pairing curriculum | nearest: decided here, once (see _pair); `pair_distance` = float64 [n] in loader order, in
+        # random mode computed on first access only; `pairing_fallbacks` = the targets `nearest` found no neighbour for
+        self.pairing_fallbacks = []
+        self._pair_distance = None
+        if self.pairing != "random":
+            self._pair(data, 0.0 if ratio is None else float(ratio))
         self.decoded = decoded
         self.world = (getattr(opt, "world_size", 1) or 1) if getattr(opt, "distributed", False) else 1
         self.rank = torch.distributed.get_rank() if (self.world > 1 and torch.distributed.is_initialized()) else 0
@@ -271,6 +326,62 @@ class HandFolderLoader:
         random.shuffle(src)
         return src, tgt
 
+    # ------------------------------------------------------------------ pose-distance pairing
+    def pose_of(self, image_path):
+        """float64 [21,3] = (u, v, depth / 700 * 255) of an image, at the files' own size: what load_sample hands out as C1 / C2
+        (--resize_inputs does not touch it, so the pairing does not depend on that flag)"""
+        a = self.get_labels(image_path)
+        uv = np.asarray(a["uv_coord"], dtype=np.float64).reshape(21, 2)
+        z = np.expand_dims(np.asarray(a["depth"], dtype=np.float64), -1) / 700.0 * 255
+        return np.concatenate([uv, z], axis=-1)
+
+    def _features(self, paths):
+        poses = np.stack([self.pose_of(p) for p in paths])
+        return ops.pose_features(torch.from_numpy(poses).to(self.device).contiguous())
+
+    def _distances(self):
+        """pose distance of every (source, target) pair in the lists' present order, float64 [n] on the host"""
+        with torch.cuda.device(self.device):
+            d = ops.pose_pair_distance(self._features(self.image_source), self._features(self.image_target))
+            return d.cpu().numpy()
+
+    @property
+    def pair_distance(self):
+        if self._pair_distance is None:
+            self._pair_distance = self._distances()
+        return self._pair_distance
+
+    def _pair(self, data, ratio):
+        """curriculum: the random pairs as they are, fed from the smallest pose distance to the largest.  nearest: the source
+        of every target is its nearest pose in the pool - the targets themselves without the target (self), or the training
+        share data[sep:] of the same root (train; `data` is the sorted list _get_src_tgt cut)."""
+        if self.pairing == "curriculum":
+            d = self._distances()
+            order = curriculum_order(d)
+            self.image_source = [self.image_source[i] for i in order]
+            self.image_target = [self.image_target[i] for i in order]
+            self._pair_distance = d[order]
+            return
+        if self.match_pool == "train":
+            if "test" in self.root_dir:
+                raise ValueError(f"--match_pool train: {self.root_dir!r} is a 'test' directory, it has no training share")
+            if self.opt.isTrain:
+                raise ValueError("--match_pool train serves a generation split (isTrain False): a training loader's targets "
+                                 "ARE the training share (--match_pool self)")
+            pool = data[int((1 - ratio) * len(data)):]
+            if not pool:
+                raise ValueError(f"--match_pool train: --augmentation_ratio {ratio} leaves no training share in {self.root_dir!r}")
+        else:
+            pool = self.image_target
+        with torch.cuda.device(self.device):
+            q = self._features(self.image_target)
+            c = q if pool is self.image_target else self._features(pool)
+            exclude = torch.arange(len(pool), dtype=torch.int32, device=self.device) if pool is self.image_target else None
+            idx, _ = ops.pose_knn(q, c, 1, exclude=exclude)
+            idx = idx.cpu().numpy()
+        self.image_source, self.pairing_fallbacks = apply_nearest(self.image_source, pool, idx)
+        self._pair_distance = self._distances()
+
     def get_labels(self, image_path):
         *_, folder, name = image_path.split("/")
         if "joints" in name:
@@ -285,6 +396,12 @@ class HandFolderLoader:
         n = len(self.image_source)
         if self.world <= 1:
             return list(range(n))
+        if self.pairing == "curriculum":
+            # no permutation: the padded range, rank-strided, so that all ranks step through the same difficulty together
+            total = -(-n // self.world) * self.world
+            idx = list(range(n))
+            idx += (idx * -(-(total - n) // n))[:total - n]
+            return idx[self.rank:total:self.world]
         g = torch.Generator().manual_seed(0 + self.epoch)
         idx = torch.randperm(n, generator=g).tolist()
         total = -(-n // self.world) * self.world

@@ -6,7 +6,7 @@ scores each output against its target image H2:
 
     python -m mmhand_amd.evaluate --name CKP [--checkpoints_dir checkpoints] [--which_epoch latest] --dataroot DIR
         --dataset rhd|stb [--augmentation_ratio R] [--batchSize 16] [--bf16] [--gpu 0] [--window 11]
-        [--resize_inputs N] [--results_json PATH] [--per_image_csv PATH]
+        [--resize_inputs N] [--pairing P [--match_pool M]] [--results_json PATH] [--per_image_csv PATH]
 
 Directory mode - scores the PNGs aug.py wrote (<DIR>/<folder of the target>/<name>) against the target colour PNGs:
 
@@ -14,6 +14,12 @@ Directory mode - scores the PNGs aug.py wrote (<DIR>/<folder of the target>/<nam
 
 `--resize_inputs N`: the pairs are decoded to N x N inside the device's decode pass (ops.decode_inputs; what `train` and `aug`
 do under the same flag); directory mode then expects N x N PNGs and scores them against the targets decoded at that size.
+
+`--pairing random|curriculum|nearest [--match_pool self|train]`: the loader's pairing (data.HandFolderLoader; what `aug` does
+under the same flags).  SSIM, L1 and PSNR of a generated image depend strongly on how far the source pose is from the target
+pose; with the flag given the results JSON also carries `pairing` and `pose_distance_avg` (the reference's pose distance,
+nearest_neighbor_search.py:68-83, mean over the scored pairs) and the per-image CSV a `pose_distance` column.  Without the
+flag both files are what they were.
 
 Both print one summary line (SSIM_avg, SSIM_std, L1_avg, PSNR_avg, n) and write it with the options used as JSON."""
 import argparse
@@ -50,6 +56,9 @@ def build_parser():
     p.add_argument("--device_png", action="store_true", help="decode the dataset's PNGs on the device (= MMH_DEVICE_PNG=1)")
     p.add_argument("--resize_inputs", type=int, default=0,
                    help="score at N x N: the dataset's images resized inside the device's decode pass (0 = the files' size)")
+    p.add_argument("--pairing", default=None, choices=("random", "curriculum", "nearest"),
+                   help="how a target gets its source (as aug's flag); given, the outputs also report the pairs' pose distance")
+    p.add_argument("--match_pool", default=None, choices=("self", "train"), help="with --pairing nearest: the sources' pool")
     p.add_argument("--window", type=int, default=11, help="SSIM window, odd, 3 .. 15 (the reference's default 11)")
     p.add_argument("--results_json", default=None,
                    help="default: <checkpoints_dir>/<name>/eval_<which_epoch>_<dataset>.json, or <generated>/eval_<dataset>.json")
@@ -92,7 +101,16 @@ def _opt(args):
                                                                           args.augmentation_ratio, False)
     opt.device_png = bool(getattr(args, "device_png", False))
     opt.resize_inputs = int(getattr(args, "resize_inputs", 0) or 0)
+    opt.pairing, opt.match_pool = getattr(args, "pairing", None) or "random", getattr(args, "match_pool", None) or "self"
     return opt
+
+
+def _pose_distances(args, loader):
+    """{(target, source): pose distance} of the loader's pairs when --pairing is given, else None (nothing is launched)"""
+    if not getattr(args, "pairing", None):
+        return None
+    d = loader.pair_distance
+    return {(t, s): float(d[i]) for i, (s, t) in enumerate(zip(loader.image_source, loader.image_target))}
 
 
 def _score_generator(args, ckpt, dev):
@@ -110,7 +128,7 @@ def _score_generator(args, ckpt, dev):
         fake = gen([s["H1"], torch.cat((s["P1"], s["P2"]), 1), torch.cat((s["D1"], s["D2"]), 1)])
         # gen returns its graph's static output buffer: the metric is enqueued here, before the next replay
         meter.feed(fake, s["H2"], [{"target": t, "source": h} for t, h in zip(s["H2_path"], s["H1_path"])])
-    return meter, {"ngf": ngf, "n_blocks": n_blocks, "norm": norm, "use_dropout": use_dropout}
+    return meter, {"ngf": ngf, "n_blocks": n_blocks, "norm": norm, "use_dropout": use_dropout}, _pose_distances(args, loader)
 
 
 def _read_generated(path):
@@ -157,7 +175,7 @@ def _score_directory(args, dev):
             continue
         meter.feed(torch.from_numpy(np.stack(gen)).to(dev), torch.from_numpy(np.stack(ref)).to(dev),
                    [{"target": t, "source": s} for t, s in zip(tgts, srcs)])
-    return meter, {}
+    return meter, {}, _pose_distances(args, loader)
 
 
 def main(argv=None):
@@ -178,22 +196,31 @@ def main(argv=None):
         raise SystemExit(f"evaluate: --generated {args.generated} is not a directory")
     torch.cuda.set_device(args.gpu)
     dev = torch.device("cuda", args.gpu)
-    meter, config = _score_generator(args, ckpt, dev) if ckpt else _score_directory(args, dev)
+    meter, config, pose_d = _score_generator(args, ckpt, dev) if ckpt else _score_directory(args, dev)
     res = meter.result()
     summary = res["summary"]
+    if pose_d is not None:
+        for r in res["rows"]:
+            r["pose_distance"] = pose_d[(r["target"], r["source"])]
+        known = [r["pose_distance"] for r in res["rows"] if r["pose_distance"] == r["pose_distance"]]
+        summary["pairing"] = args.pairing
+        summary["pose_distance_avg"] = float(np.mean(known)) if known else float("nan")
     print(json.dumps(summary))
     out = args.results_json or (os.path.join(args.checkpoints_dir, args.name, f"eval_{args.which_epoch}_{args.dataset}.json")
                                 if ckpt else os.path.join(args.generated, f"eval_{args.dataset}.json"))
     os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
     with open(out, "w") as fh:
-        json.dump({"summary": summary, "options": vars(args), "generator": config or None,
+        # the pairing flags appear among the options only when --pairing was given: without it the file is what it always was
+        options = {k: v for k, v in vars(args).items() if pose_d is not None or k not in ("pairing", "match_pool")}
+        json.dump({"summary": summary, "options": options, "generator": config or None,
                    "domain": "[0, 1]: generator output (x + 1) / 2, PNG pixels u8 / 255"}, fh, indent=1)
     if args.per_image_csv:
         with open(args.per_image_csv, "w", newline="") as fh:
             w = csv.writer(fh)
-            w.writerow(["target", "source", "ssim", "l1", "psnr"])
+            extra = ["pose_distance"] if pose_d is not None else []
+            w.writerow(["target", "source", "ssim", "l1", "psnr"] + extra)
             for r in res["rows"]:
-                w.writerow([r["target"], r["source"], repr(r["ssim"]), repr(r["l1"]), repr(r["psnr"])])
+                w.writerow([r["target"], r["source"], repr(r["ssim"]), repr(r["l1"]), repr(r["psnr"])] + [repr(r[k]) for k in extra])
     return res
 
 

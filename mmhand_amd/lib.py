@@ -200,6 +200,10 @@ SIGNATURES = {
     "mmh_png_encode_slot_bytes": (_i64, [_i, _i]),
     "mmh_png_encode_scratch_bytes": (_i64, [_i, _i, _i]),
     "mmh_png_encode_batch": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "mmh_pose_features": (_i, [_vp, _i, _vp, _vp, _vp]),
+    "mmh_pose_knn_ws_bytes": (_sz, [_i, _i, _i, _i]),
+    "mmh_pose_knn": (_i, [_vp, _vp, _i, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp]),
+    "mmh_pose_pair_distance": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp]),
 }
 
 _lib = None

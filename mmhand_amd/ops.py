@@ -3294,3 +3294,58 @@ def decode_inputs_indexed(store, idx, uv_table, out_size=None, sigma=6.0, status
     L.call("mmh_decode_inputs_indexed", _ptr(store), S, Hs, Ws, _ptr(idx), _ptr(uv_table), B, Ho, Wo, float(sigma),
            _ptr(xh1), _ptr(xh2), _ptr(xp), _ptr(xd), _ptr(status), _stream())
     return xh1, xh2, xp, xd
+
+
+# ----------------------------------------------------------------------------- pose distance (csrc/pose_knn.hip)
+def _chk_pose_features(F, valid, what):
+    assert F.is_cuda and F.dtype == torch.float64 and F.is_contiguous() and F.dim() == 2 and F.shape[1] == 64 and \
+        F.shape[0] >= 1, f"{what}: contiguous float64 CUDA [N,64] features (ops.pose_features)"
+    assert valid.dtype == torch.int32 and valid.device == F.device and valid.is_contiguous() and \
+        tuple(valid.shape) == (F.shape[0],), f"{what}: valid is a contiguous int32 [N] on the features' device"
+
+
+def pose_features(C_):
+    """Poses float64 [N,21,3] = (u, v, depth / 700 * 255) on the device -> (F float64 [N,64], valid int32 [N]): the reference's
+    identity() (nearest_neighbor_search.py:68-83) - the 20 consecutive joint differences, divided by their 2-norm, 4 zeros of
+    padding.  A pose with a non-finite coordinate or a zero norm has valid = 0 and a zero row."""
+    assert C_.is_cuda and C_.dtype == torch.float64 and C_.is_contiguous() and C_.dim() == 3 and \
+        tuple(C_.shape[1:]) == (21, 3) and C_.shape[0] >= 1, "poses: contiguous float64 CUDA [N,21,3]"
+    N = C_.shape[0]
+    F = torch.empty((N, 64), dtype=torch.float64, device=C_.device)
+    valid = torch.empty((N,), dtype=torch.int32, device=C_.device)
+    L.call("mmh_pose_features", _ptr(C_), N, _ptr(F), _ptr(valid), _stream())
+    return F, valid
+
+
+def pose_knn(q, c, k, exclude=None, cand_split=0):
+    """q, c: (F, valid) pairs of pose_features (queries, candidates) -> (idx int32 [Nq,k], dist float64 [Nq,k]): the k nearest
+    candidates of every query under d = arccos(clamp(cos, -1, 1)) / pi, nearest first, ties by the smaller index.  exclude:
+    int32 [Nq] on the device, one candidate per query that is never returned (-1 = none).  Unfilled slots are -1 / NaN.
+    cand_split: candidates per slice (a multiple of 16; 0 = automatic) - the result does not depend on it, bit for bit."""
+    (Fq, vq), (Fc, vc) = q, c
+    _chk_pose_features(Fq, vq, "queries")
+    _chk_pose_features(Fc, vc, "candidates")
+    assert Fc.device == Fq.device, "queries and candidates live on one device"
+    Nq, Nc, k, cand_split = Fq.shape[0], Fc.shape[0], int(k), int(cand_split)
+    if exclude is not None:
+        assert exclude.dtype == torch.int32 and exclude.device == Fq.device and exclude.is_contiguous() and \
+            tuple(exclude.shape) == (Nq,), "exclude: contiguous int32 [Nq] on the queries' device"
+    need = L.load().mmh_pose_knn_ws_bytes(Nq, Nc, k, cand_split)
+    ws = torch.empty((max(int(need), 8),), dtype=torch.uint8, device=Fq.device)
+    idx = torch.empty((Nq, max(k, 0)), dtype=torch.int32, device=Fq.device)
+    dist = torch.empty((Nq, max(k, 0)), dtype=torch.float64, device=Fq.device)
+    L.call("mmh_pose_knn", _ptr(Fq), _ptr(vq), Nq, _ptr(Fc), _ptr(vc), Nc, _ptr(exclude), k, cand_split, _ptr(ws), _ptr(idx),
+           _ptr(dist), _stream())
+    return idx, dist
+
+
+def pose_pair_distance(a, b):
+    """a, b: (F, valid) pairs of pose_features with the same N -> float64 [N]: the pose distance of pair i, NaN if either
+    pose is invalid"""
+    (Fa, va), (Fb, vb) = a, b
+    _chk_pose_features(Fa, va, "a")
+    _chk_pose_features(Fb, vb, "b")
+    assert Fa.shape == Fb.shape and Fa.device == Fb.device, "a and b: the same number of poses on one device"
+    d = torch.empty((Fa.shape[0],), dtype=torch.float64, device=Fa.device)
+    L.call("mmh_pose_pair_distance", _ptr(Fa), _ptr(va), _ptr(Fb), _ptr(vb), Fa.shape[0], _ptr(d), _stream())
+    return d

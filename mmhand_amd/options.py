@@ -25,7 +25,9 @@ Differences, all deliberate:
     files hold - the resize happens inside the device's decode pass (ops.decode_inputs).  --fineSize keeps the dead
     meaning it has in the reference (declared, never read);
   * --resident_dataset / --resident_gb G (additions; off): the file-fed loader keeps the decoded dataset in device memory
-    after the first epoch (data.HandFolderLoader(resident=True)).
+    after the first epoch (data.HandFolderLoader(resident=True));
+  * --pairing random | curriculum | nearest, --match_pool self | train (additions; random = the reference's live loader):
+    the paper's pairing strategies on the reference's pose distance (data.HandFolderLoader, csrc/pose_knn.hip).
 """
 import argparse
 import os
@@ -109,6 +111,13 @@ _BASE = [
                                 "default is a policy choice - under a quarter of a 288 GB card - not a measured number; a "
                                 "dataset over it (or over the free memory) leaves the loader on the file path, whole: there "
                                 "is no partial store")),
+    ("--pairing", dict(type=str, default="random", choices=["random", "curriculum", "nearest"],
+                       help="with --dataroot: how a target gets its source - random: the reference's shuffle; curriculum: the "
+                            "same random pairs, fed from the smallest pose distance (nearest_neighbor_search.py:68-83) to the "
+                            "largest, every epoch; nearest: the source whose 3D pose is closest to the target's")),
+    ("--match_pool", dict(type=str, default="self", choices=["self", "train"],
+                          help="with --pairing nearest: where the sources come from - self: the loader's own targets, the target "
+                               "itself excluded; train: the training share of the same --dataroot, for a generation split")),
 ]
 _TRAIN = [
     ("--display_freq", dict(type=int, default=100)),
