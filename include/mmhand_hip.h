@@ -77,8 +77,22 @@ int mmh_version(void);
  * "lp16_dbg" (bits 1-16), "dgrad_s2_dbg", "stem_f32_dbg" switch parts of a kernel OFF for timing
  * ablations (tools/ablate*.py, tools/bench_lp16_fold.py) and make its results wrong ("lp16_dbg" bit 32 only
  * moves the DMA issue of half the waves, results unchanged: tools/ab_lp16_stagger.py); they default to 0
- * and nothing in mmhand_amd/ sets them.  Unknown keys are an error.                       */
+ * and nothing in mmhand_amd/ sets them.  Unknown keys are an error.
+ * Every key (mmh_option_key enumerates the same list):
+ *   fp32 implicit GEMM   "conv_dbuf" "conv_cw" "conv_bn256" "conv_levels" (1 | 2) "conv_xcd" "conv_xcd1" "conv_tall"
+ *                        "dgrad_s2_multi" "dgrad_s2_halo" "border_bn64" "stem_f32"
+ *   fp32 wgrad           "wgrad_slots" "wgrad_dbuf" "wgrad_bn256" "wgrad_xcd" "wgrad_s2_strip" "slab_reduce_par"
+ *   fp32 Winograd        "wino_bn256" "wino_xcd" "wino_gemm_v2" "wino_gemm_occ" "wino_gemm_bn" "wino_gemm_levels"
+ *                        "wino_bf16_bk" "wino_bf16_occ" "wino6_vec" "wino_wgrad_v2" "wino_wgrad_occ"
+ *                        "wino_wgrad_bn256" "wino_wgrad_slots" "wino_wgrad_dma"
+ *   16-bit kernels       "lp16_shape" "lp16_s2f" "lp16_persist" "lp16_tap_inner" "lp16_wgrad_ring" "lp16_wgrad_s2"
+ *   pointwise            "pw_v2" "col_chunks" "row_chunks" (the last two: values > 0 only)
+ *   ablation switches    "conv_dbg" "lp16_dbg" "dgrad_s2_dbg" "stem_f32_dbg"                                  */
 int mmh_set_option(const char* key, int value);
+/* The current value of a key (to restore it after an A/B); unknown keys are an error. */
+int mmh_get_option(const char* key, int* value);
+/* The index-th key of the list above, NULL past its end. */
+const char* mmh_option_key(int index);
 
 /* ---- convolutions: nn.Conv2d / nn.ReflectionPad2d / nn.ConvTranspose2d ----
  * replaces models/Generator.py:40-113,158-259, models/Discriminator.py:14-99,

@@ -3178,57 +3178,93 @@ int do_wgrad(const mmh_conv_desc* d, const void* x, const void* dy, void* dw, vo
     return mmh::launch_slab_reduce(p.slab, static_cast<float*>(dw), n4, splits, accumulate, n4, st);
 }
 
+// Every mmh_set_option / mmh_get_option key and the global it names: the one list both functions (and mmh_option_key) walk.
+struct OptionEntry { const char* name; int* value; };
+const OptionEntry* option_table(int* count) {
+    static const OptionEntry table[] = {
+        {"conv_dbuf", &g_conv_dbuf},
+        {"conv_dbg", &g_conv_dbg},
+        {"conv_cw", &g_conv_cw},
+        {"conv_bn256", &g_conv_bn256},
+        {"conv_levels", &g_conv_levels},
+        {"wino_bn256", &g_wino_bn256},
+        {"conv_xcd", &g_conv_xcd},
+        {"conv_xcd1", &g_conv_xcd1},
+        {"conv_tall", &g_conv_tall},
+        {"wgrad_slots", &g_wgrad_slots},
+        {"wgrad_dbuf", &g_wgrad_dbuf},
+        {"wgrad_bn256", &g_wgrad_bn256},
+        {"wgrad_xcd", &g_wgrad_xcd},
+        {"wino_wgrad_v2", &g_wino_wgrad_v2},
+        {"wino_wgrad_occ", &g_wino_wgrad_occ},
+        {"wino_gemm_v2", &g_wino_gemm_v2},
+        {"wino_xcd", &g_wino_xcd},
+        {"dgrad_s2_multi", &g_dgrad_s2_multi},
+        {"wino6_vec", &mmh::g_wino6_vec},
+        {"lp16_shape", &mmh::g_lp16_shape},
+        {"lp16_s2f", &mmh::g_lp16_s2f},
+        {"lp16_persist", &mmh::g_lp16_persist},
+        {"lp16_tap_inner", &mmh::g_lp16_tap_inner},
+        {"pw_v2", &mmh::g_pw_v2},
+        {"col_chunks", &mmh::g_col_chunks},
+        {"row_chunks", &mmh::g_row_chunks},
+        {"dgrad_s2_halo", &mmh::g_dgrad_s2_halo},
+        {"wgrad_s2_strip", &mmh::g_wgrad_s2_strip},
+        {"stem_f32", &mmh::g_stem_f32},
+        {"wino_wgrad_dma", &mmh::g_wino_wgrad_dma},
+        {"stem_f32_dbg", &mmh::g_stem_f32_dbg},
+        {"slab_reduce_par", &mmh::g_slab_reduce_par},
+        {"dgrad_s2_dbg", &mmh::g_dgrad_s2_dbg},
+        {"lp16_dbg", &mmh::g_lp16_dbg},
+        {"lp16_wgrad_ring", &mmh::g_lp16_wgrad_ring},
+        {"lp16_wgrad_s2", &mmh::g_lp16_wgrad_s2},
+        {"border_bn64", &g_border_bn64},
+        {"wino_gemm_occ", &g_wino_gemm_occ},
+        {"wino_gemm_levels", &g_wino_gemm_levels},
+        {"wino_gemm_bn", &g_wino_gemm_bn},
+        {"wino_bf16_occ", &g_wino_bf16_occ},
+        {"wino_bf16_bk", &g_wino_bf16_bk},
+        {"wino_wgrad_bn256", &g_wino_wgrad_bn256},
+        {"wino_wgrad_slots", &g_wino_wgrad_slots},
+    };
+    *count = (int)(sizeof(table) / sizeof(table[0]));
+    return table;
+}
+const OptionEntry* find_option(const char* key) {
+    int n = 0;
+    const OptionEntry* t = option_table(&n);
+    for (int i = 0; i < n; ++i)
+        if (!strcmp(key, t[i].name)) return &t[i];
+    return nullptr;
+}
+
 }  // namespace
 
 extern "C" {
 
 int mmh_set_option(const char* key, int value) {
     MMH_REQUIRE(key != nullptr, "mmh_set_option: NULL key");
-    if (!strcmp(key, "conv_dbuf")) { g_conv_dbuf = value; return 0; }
-    if (!strcmp(key, "conv_dbg")) { g_conv_dbg = value; return 0; }
-    if (!strcmp(key, "conv_cw")) { g_conv_cw = value; return 0; }
-    if (!strcmp(key, "conv_bn256")) { g_conv_bn256 = value; return 0; }
-    if (!strcmp(key, "conv_levels")) { g_conv_levels = value == 2 ? 2 : 1; mmh::g_stem_f32_levels = g_conv_levels; return 0; }
-    if (!strcmp(key, "wino_bn256")) { g_wino_bn256 = value; return 0; }
-    if (!strcmp(key, "conv_xcd")) { g_conv_xcd = value; return 0; }
-    if (!strcmp(key, "conv_xcd1")) { g_conv_xcd1 = value; return 0; }
-    if (!strcmp(key, "conv_tall")) { g_conv_tall = value; return 0; }
-    if (!strcmp(key, "wgrad_slots")) { g_wgrad_slots = value; return 0; }
-    if (!strcmp(key, "wgrad_dbuf")) { g_wgrad_dbuf = value; return 0; }
-    if (!strcmp(key, "wgrad_bn256")) { g_wgrad_bn256 = value; return 0; }
-    if (!strcmp(key, "wgrad_xcd")) { g_wgrad_xcd = value; return 0; }
-    if (!strcmp(key, "wino_wgrad_v2")) { g_wino_wgrad_v2 = value; return 0; }
-    if (!strcmp(key, "wino_wgrad_occ")) { g_wino_wgrad_occ = value; return 0; }
-    if (!strcmp(key, "wino_gemm_v2")) { g_wino_gemm_v2 = value; return 0; }
-    if (!strcmp(key, "wino_xcd")) { g_wino_xcd = value; return 0; }
-    if (!strcmp(key, "dgrad_s2_multi")) { g_dgrad_s2_multi = value; return 0; }
-    if (!strcmp(key, "wino6_vec")) { mmh::g_wino6_vec = value; return 0; }
-    if (!strcmp(key, "lp16_shape")) { mmh::g_lp16_shape = value; return 0; }
-    if (!strcmp(key, "lp16_s2f")) { mmh::g_lp16_s2f = value; return 0; }
-    if (!strcmp(key, "lp16_persist")) { mmh::g_lp16_persist = value; return 0; }
-    if (!strcmp(key, "lp16_tap_inner")) { mmh::g_lp16_tap_inner = value; return 0; }
-    if (!strcmp(key, "pw_v2")) { mmh::g_pw_v2 = value; return 0; }
-    if (!strcmp(key, "col_chunks") && value > 0) { mmh::g_col_chunks = value; return 0; }
-    if (!strcmp(key, "row_chunks") && value > 0) { mmh::g_row_chunks = value; return 0; }
-    if (!strcmp(key, "dgrad_s2_halo")) { mmh::g_dgrad_s2_halo = value; return 0; }
-    if (!strcmp(key, "wgrad_s2_strip")) { mmh::g_wgrad_s2_strip = value; return 0; }
-    if (!strcmp(key, "stem_f32")) { mmh::g_stem_f32 = value; return 0; }
-    if (!strcmp(key, "wino_wgrad_dma")) { mmh::g_wino_wgrad_dma = value; return 0; }
-    if (!strcmp(key, "stem_f32_dbg")) { mmh::g_stem_f32_dbg = value; return 0; }
-    if (!strcmp(key, "slab_reduce_par")) { mmh::g_slab_reduce_par = value; return 0; }
-    if (!strcmp(key, "dgrad_s2_dbg")) { mmh::g_dgrad_s2_dbg = value; return 0; }
-    if (!strcmp(key, "lp16_dbg")) { mmh::g_lp16_dbg = value; return 0; }
-    if (!strcmp(key, "lp16_wgrad_ring")) { mmh::g_lp16_wgrad_ring = value; return 0; }
-    if (!strcmp(key, "lp16_wgrad_s2")) { mmh::g_lp16_wgrad_s2 = value; return 0; }
-    if (!strcmp(key, "border_bn64")) { g_border_bn64 = value; return 0; }
-    if (!strcmp(key, "wino_gemm_occ")) { g_wino_gemm_occ = value; return 0; }
-    if (!strcmp(key, "wino_gemm_levels")) { g_wino_gemm_levels = value; return 0; }
-    if (!strcmp(key, "wino_gemm_bn")) { g_wino_gemm_bn = value; return 0; }
-    if (!strcmp(key, "wino_bf16_occ")) { g_wino_bf16_occ = value; return 0; }
-    if (!strcmp(key, "wino_bf16_bk")) { g_wino_bf16_bk = value; return 0; }
-    if (!strcmp(key, "wino_wgrad_bn256")) { g_wino_wgrad_bn256 = value; return 0; }
-    if (!strcmp(key, "wino_wgrad_slots")) { g_wino_wgrad_slots = value; return 0; }
-    return mmh::fail("mmh_set_option: unknown key '%s'", key);
+    const OptionEntry* e = find_option(key);
+    if (!e) return mmh::fail("mmh_set_option: unknown key '%s'", key);
+    if (e->value == &g_conv_levels) { g_conv_levels = value == 2 ? 2 : 1; mmh::g_stem_f32_levels = g_conv_levels; return 0; }
+    if (e->value == &mmh::g_col_chunks || e->value == &mmh::g_row_chunks)
+        MMH_REQUIRE(value > 0, "mmh_set_option: '%s' needs a value > 0, got %d", key, value);
+    *e->value = value;
+    return 0;
+}
+
+int mmh_get_option(const char* key, int* value) {
+    MMH_REQUIRE(key != nullptr && value != nullptr, "mmh_get_option: NULL key or value");
+    const OptionEntry* e = find_option(key);
+    if (!e) return mmh::fail("mmh_get_option: unknown key '%s'", key);
+    *value = *e->value;
+    return 0;
+}
+
+const char* mmh_option_key(int index) {
+    int n = 0;
+    const OptionEntry* t = option_table(&n);
+    return index >= 0 && index < n ? t[index].name : nullptr;
 }
 
 int mmh_conv2d_fprop(const mmh_conv_desc* d, const void* x, const void* w, const void* bias,

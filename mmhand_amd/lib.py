@@ -51,6 +51,8 @@ SIGNATURES = {
     "mmh_pool_exchange": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i64, _vp]),
     "mmh_version": (_i, []),
     "mmh_set_option": (_i, [C.c_char_p, _i]),
+    "mmh_get_option": (_i, [C.c_char_p, C.POINTER(_i)]),
+    "mmh_option_key": (C.c_char_p, [_i]),
     "mmh_conv2d_fprop": (_i, [_DP, _vp, _vp, _vp, _vp, _i, _vp]),
     "mmh_conv2d_fprop_stats_chunks": (_i, [_DP]),
     "mmh_conv2d_fprop_stats": (_i, [_DP, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -243,6 +245,22 @@ def check(rc, what):
     if rc != 0:
         msg = load().mmh_last_error()
         raise RuntimeError(f"{what} failed: {msg.decode() if msg else 'unknown error'}")
+
+
+def get_option(key):
+    """current value of an mmh_set_option key (str or bytes)"""
+    v = C.c_int(0)
+    check(load().mmh_get_option(key.encode() if isinstance(key, str) else key, C.byref(v)), "mmh_get_option")
+    return v.value
+
+
+def option_keys():
+    """every mmh_set_option key, in the library's own order"""
+    fn, out, i = load().mmh_option_key, [], 0
+    while (k := fn(i)) is not None:
+        out.append(k.decode())
+        i += 1
+    return out
 
 
 def call(name, *args):

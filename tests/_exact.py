@@ -17,6 +17,7 @@ non-zero; bias in {-2 .. 2}; addend within +-8.
 The case lists of tests/test_conv_exact_gpu.py live here, so that tests/test_conv_exact_cpu.py checks the caps of every
 (shape, density) pair without a GPU.
 """
+import contextlib
 import functools
 from types import SimpleNamespace
 
@@ -97,7 +98,33 @@ def assert_rounds(got, want, what):
     return worst
 
 
-@functools.lru_cache(maxsize=6)
+@contextlib.contextmanager
+def option(key, value):
+    """mmh_set_option(key, value) for the body, then back to the value the key HAD (mmh_get_option), not to a default this file
+    believes in; asserts that the restore took.  Options are process-global and the suite runs in one process."""
+    from mmhand_amd import lib
+    key = key.encode() if isinstance(key, str) else key
+    old = lib.get_option(key)
+    lib.check(lib.load().mmh_set_option(key, int(value)), "mmh_set_option")       # not lib.call: a test's spy counts kernels only
+    try:
+        yield old
+    finally:
+        lib.check(lib.load().mmh_set_option(key, old), "mmh_set_option")
+        assert lib.get_option(key) == old, (key, old, lib.get_option(key))
+
+
+@contextlib.contextmanager
+def options(**kv):
+    """several option()s at once: options(conv_xcd=0, conv_bn256=0)"""
+    with contextlib.ExitStack() as stack:
+        for k, v in kv.items():
+            stack.enter_context(option(k, v))
+        yield
+
+
+# one entry per distinct problem of the case lists below, so that every oracle is computed once per process whatever the order
+# of the tests (70 problems; the two 364 x 364 ones hold about 0.3 GB between them)
+@functools.lru_cache(maxsize=96)
 def problem(B, H, W, Cin, Cout, k, stride, pad, reflect, act=0, cap_y=CAP_F32, cap_dx=CAP_F32, density=W_DENSITY, kind="conv"):
     """One seeded integer problem and its oracle, computed once and shared (read-only!) by the tests that need it.
     kind "conv": Conv2d.  kind "convT": ConvTranspose2d(k3, s2, p1, op1) with x [B,H,W,Cin], w [3,3,Cout,Cin].
@@ -172,6 +199,51 @@ WINO24 = [(1, 12, 20, 256, 256, True), (2, 8, 8, 64, 128, False)]
 WINO2_FWD = [(2, 12, 20, 256, 256, True)]
 WINO_WGRAD_DMA = (16, 64, 256, 256)     # (planes, tiles, Cin, Cout) of tests/test_wino_gemm_gpu.py
 
+# ---------------------------------------------------------------------------- variants and partitions (round 2 of this file)
+# The lists above run every family at its smallest ragged shapes; most dispatch decisions in csrc/ sit ABOVE those shapes.
+# Each case below is there for one branch; its comment gives the arithmetic that selects it (BM = 128 rows per tile, BK = 32).
+# tests/test_conv_variants_gpu.py runs them, tests/test_conv_exact_cpu.py checks their caps and the host-only queries.
+
+# fp32 implicit GEMM, 3x3 s1 reflect -------------------------------------------------------------------------
+IGEMM_BN128 = [(1, 9, 11, 16, 128),      # 64 < N, N % 256 != 0: conv_igemm_kernel<128,2,2> (and <..., DBUF> with conv_dbuf)
+               (1, 9, 11, 16, 256)]      # conv_bn256 = 0: the same template with gx = 2
+IGEMM_XCD = [(1, 33, 35, 8, 192),        # M = 1155: gy = 10 >= 8, band = 1: 8 row tiles remapped, 2 keep their ids, the last holds
+                                         # 3 rows; gx = 2 on the 128 template, the second column tile half empty
+             (1, 33, 35, 8, 512),        # the 256-wide template, gx = 2, same rows
+             (1, 33, 35, 8, 64),         # gx = 1: remapped only because of conv_xcd1
+             (1, 32, 32, 8, 192),        # M = 1024: gy = 8, no ragged rest
+             (1, 33, 35, 192, 8)]        # dgrad: N = Cin = 192, gx = 2, gy = 10 (the main piece of the folded dgrad)
+IGEMM_CW = [(1, 15, 17, 128, 64),        # Cin = 128: 4 chunks of 32 per tap: conv_cw 1, 2 (= auto), 4; M = 255
+            (1, 15, 17, 96, 64)]         # Cin = 96: 3 chunks: auto 1, conv_cw 3
+IGEMM_TALL = [(1, 364, 364, 4, 64)]      # conv_tall = 2: 32 < N <= 64 and M = 132496 >= 256 * 512, M % 256 = 144 (zero padding)
+DGRAD_S2_TALL = [(1, 364, 364, 64, 8)]   # stride-2 dgrad, 32 < Cin <= 64, M per parity class = 182 * 182 = 33124 >= 256 * 128: the
+                                         # 256-row multi-piece kernel (conv_tall = 1); Cout = 8 keeps it off the halo kernel
+
+# fp32 wgrad, 3x3 s1 reflect: Mrows = 9 * Cin <= 128 and N <= 128 give one tile, so splits = P / 256 ---------
+WGRAD_SPLITS = [(1, 5, 461, 8, 32),      # P = 2305: 9 splits of 288 pixels, the last has 1
+                (1, 13, 197, 8, 32),     # P = 2561: 10 splits of 288, split 9 is empty
+                (2, 64, 65, 8, 32),      # P = 8320: 32 splits of 288, 29..31 empty: slab_reduce_par_kernel<8>
+                (1, 40, 135, 8, 32)]     # P = 5400: 21 splits: slab_reduce_par_kernel<4>, one unrolled round + remainder 16, 20
+WGRAD_SPLITS_N = {2305: 9, 2561: 10, 8320: 32, 5400: 21}
+WGRAD_SLOTS = (4, 4)                     # wgrad_slots = 4 at P = 2305: 4 splits fill one round of 4 slots, 9 do not
+WGRAD_TEMPLATES = [(2, 9, 11, 12, 128),  # Mrows = 108 (ragged over 128); <128,2,2> and, with wgrad_dbuf, its DBUF form
+                   (2, 9, 11, 12, 256),  # <256,2,2>; wgrad_bn256 = 0: <128,2,2> with two column tiles
+                   (2, 9, 11, 12, 48),   # <64,2,2>, 16 columns masked
+                   (2, 9, 11, 12, 20)]   # <32,4,1>, 12 columns masked
+
+# fp32 Winograd F(6x6,3x3) (held to `round`) -----------------------------------------------------------------
+WINO_PERSIST = [(2, 72, 72, 64, 256, True)]   # 288 tiles: MT = 3, NT = 2, W = 64 * 6 = 384, Wx = 48 > 32 * occ at wino_gemm_occ = 1;
+                                              # K = 64 > WINO_FOLD * BK: the two-level fold; input transform: nblk = 288 * 64 / 256 = 72
+# Winograd-domain GEMMs at the stage level (integer operands: plain GEMMs, exact) ---------------------------
+WINO_WGRAD_PERSIST = (64, 2403, 128, 256)     # (planes, tiles, Cin, Cout): 9 splits of 288 tiles (the last has 99), MT = 1, NT = 2:
+                                              # W = 64 * 9 * 2 = 1152, Wx = 144 > 32 * 4: two items per workgroup at occ 3 and 4
+WINO_BF16_PERSIST = (16, 1100, 256, 512)      # (planes, tiles, K, N): MT = 9, NT = 4: W = 576, Wx = 72 > 64 (bk 128) and > 32 (occ 1)
+
+# 16-bit halo kernel, persistent: more than 256 (16 x 16-pixel, 256-channel) tiles on 256 CUs ---------------------
+HALO_PERSIST_FPROP = [(1, 184, 184, 64, 512, True)]     # 12 x 12 ragged pixel tiles x 2 column tiles = 288
+HALO_PERSIST_DGRAD = [(1, 192, 192, 512, 64)]           # dgrad: N = Cin = 512: 12 x 12 x 2 = 288; multiples of 16: mode 2 folds
+HALO_TILE, HALO_TBN = 16, 256
+
 _B16 = dict(cap_y=CAP_BF16, cap_dx=CAP_BF16)
 
 FAMILIES = {
@@ -207,6 +279,16 @@ FAMILIES = {
     "wino6": (WINO6, lambda c: _conv(c[0], c[1], c[2], c[3], c[4], 3, 1, 1, c[5])),
     "wino24": (WINO24, lambda c: _conv(c[0], c[1], c[2], c[3], c[4], 3, 1, 1, c[5], 0)),
     "wino2_fwd": (WINO2_FWD, lambda c: _conv(c[0], c[1], c[2], c[3], c[4], 3, 1, 1, c[5])),
+    "igemm_bn128": (IGEMM_BN128, lambda c: _conv(*c, 3, 1, 1, True)),
+    "igemm_xcd": (IGEMM_XCD, lambda c: _conv(*c, 3, 1, 1, True)),
+    "igemm_cw": (IGEMM_CW, lambda c: _conv(*c, 3, 1, 1, True)),
+    "igemm_tall": (IGEMM_TALL, lambda c: _conv(*c, 3, 1, 1, False)),
+    "dgrad_s2_tall": (DGRAD_S2_TALL, lambda c: _conv(*c, 3, 2, 1, False)),
+    "wgrad_splits": (WGRAD_SPLITS, lambda c: _conv(*c, 3, 1, 1, True)),
+    "wgrad_templates": (WGRAD_TEMPLATES, lambda c: _conv(*c, 3, 1, 1, True)),
+    "wino_persist": (WINO_PERSIST, lambda c: _conv(c[0], c[1], c[2], c[3], c[4], 3, 1, 1, c[5])),
+    "halo_persist_fprop": (HALO_PERSIST_FPROP, lambda c: _conv(c[0], c[1], c[2], c[3], c[4], 3, 1, 1, c[5], 0, **_B16)),
+    "halo_persist_dgrad": (HALO_PERSIST_DGRAD, lambda c: _conv(*c, 3, 1, 1, True, 0, cap_dx=CAP_BF16)),
 }
 
 

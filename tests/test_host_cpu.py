@@ -104,6 +104,129 @@ def test_round5_entry_points_plan_and_validate_without_gpu(built_lib):
     assert b"mmh_pack_nhwc_lp16" in l.mmh_last_error()
 
 
+def _option_keys_of_the_header():
+    """the quoted keys of the comment block in front of mmh_set_option's declaration"""
+    hdr = open(os.path.join(ROOT, "include", "mmhand_hip.h")).read()
+    end = hdr.index("int mmh_set_option(")
+    block = hdr[hdr.rindex("/*", 0, end):end]
+    return set(re.findall(r'"([a-z0-9_]+)"', block))
+
+
+ABLATION_KEYS = {"conv_dbg", "lp16_dbg", "dgrad_s2_dbg", "stem_f32_dbg"}      # make results wrong by design: no test sets them
+
+
+def test_every_option_has_a_getter_and_round_trips(built_lib):
+    """mmh_get_option reads what mmh_set_option writes, for every key of the one table both walk (mmh_option_key); the header
+    names exactly these keys; unknown keys fail in both; the special cases of the setter hold"""
+    L = built_lib
+    l = L.load()
+    keys = L.option_keys()
+    assert len(keys) == len(set(keys)) >= 44 and l.mmh_option_key(len(keys)) is None and l.mmh_option_key(-1) is None
+    assert set(keys) == _option_keys_of_the_header(), set(keys) ^ _option_keys_of_the_header()
+    assert ABLATION_KEYS <= set(keys)
+    for k in keys:
+        v = L.get_option(k)
+        assert l.mmh_set_option(k.encode(), v) == 0, k
+        assert L.get_option(k) == v, k
+    v = ctypes.c_int(-7)
+    assert l.mmh_get_option(b"no_such_key", ctypes.byref(v)) != 0 and b"no_such_key" in l.mmh_last_error() and v.value == -7
+    assert l.mmh_set_option(b"no_such_key", 1) != 0 and b"no_such_key" in l.mmh_last_error()
+    assert l.mmh_get_option(None, ctypes.byref(v)) != 0 and l.mmh_get_option(b"pw_v2", None) != 0
+    # a plain knob takes any value and gives it back
+    old = L.get_option("wgrad_slots")
+    try:
+        assert l.mmh_set_option(b"wgrad_slots", 5) == 0 and L.get_option("wgrad_slots") == 5
+    finally:
+        assert l.mmh_set_option(b"wgrad_slots", old) == 0
+    # conv_levels normalises to 1 | 2
+    old = L.get_option("conv_levels")
+    try:
+        for given, kept in ((2, 2), (7, 1), (0, 1), (1, 1)):
+            assert l.mmh_set_option(b"conv_levels", given) == 0 and L.get_option("conv_levels") == kept
+    finally:
+        assert l.mmh_set_option(b"conv_levels", old) == 0
+    # col_chunks / row_chunks refuse values <= 0 and keep what they had
+    for k in ("col_chunks", "row_chunks"):
+        old = L.get_option(k)
+        for bad in (0, -1):
+            assert l.mmh_set_option(k.encode(), bad) != 0 and L.get_option(k) == old
+        try:
+            assert l.mmh_set_option(k.encode(), 3) == 0 and L.get_option(k) == 3
+        finally:
+            assert l.mmh_set_option(k.encode(), old) == 0
+
+
+def test_every_option_key_is_set_by_some_test(built_lib):
+    """every knob that promises results "within the kernels' documented tolerances" is mentioned by a test: a new key, or a
+    test that goes away, shows up here by name"""
+    text = ""
+    for f in sorted(os.listdir(os.path.join(ROOT, "tests"))):
+        if f.endswith(".py") and f != os.path.basename(__file__):       # this file names keys without running a kernel
+            text += open(os.path.join(ROOT, "tests", f)).read()
+    missing = [k for k in built_lib.option_keys() if k not in ABLATION_KEYS and not re.search(r"\b%s\b" % re.escape(k), text)]
+    assert not missing, f"mmh_set_option keys no test mentions: {missing}"
+
+
+def test_variant_cases_reach_their_branches_without_gpu(built_lib):
+    """the host-only queries behind the branch-reached assertions of tests/test_conv_variants_gpu.py and
+    tests/test_pointwise_variants_gpu.py: a threshold that moves in csrc/ fails here, not as a test that silently stops
+    covering its branch"""
+    from tests import _exact as E
+    L = built_lib
+    l = L.load()
+    by = ctypes.byref
+    mk = lambda B, H, W, Cin, Cout, k, s, p, refl, dt=L.F32: L.ConvDesc(B, H, W, Cin, Cout, k, k, s, p, L.PAD_REFLECT if refl else L.PAD_ZERO,
+                                                                      (H + 2 * p - k) // s + 1, (W + 2 * p - k) // s + 1, Cin, Cout, dt)
+
+    def restore(key):
+        return key, L.get_option(key)
+
+    # fp32 wgrad: split counts (one tile, so P / 256), and wgrad_slots moving them
+    for B, H, W, Cin, Cout in E.WGRAD_SPLITS:
+        nbytes = l.mmh_conv2d_wgrad_ws_bytes(by(mk(B, H, W, Cin, Cout, 3, 1, 1, True)))
+        assert nbytes == E.WGRAD_SPLITS_N[B * H * W] * 9 * Cin * Cout * 4, (B, H, W)
+    assert sorted(E.WGRAD_SPLITS_N.values()) == [9, 10, 21, 32]          # < 8: sequential; 8..31: <4>, 21 % 4 != 0; >= 32: <8>
+    for Pn, s in E.WGRAD_SPLITS_N.items():
+        per = -(-(-(-Pn // s)) // 32) * 32
+        assert per == 288 and Pn - (s - 1) * per == {2305: 1, 2561: -31, 8320: -608, 5400: -360}[Pn]      # pixels of the last split
+    key, old = restore("wgrad_slots")
+    try:
+        assert l.mmh_set_option(key.encode(), E.WGRAD_SLOTS[0]) == 0
+        B, H, W, Cin, Cout = E.WGRAD_SPLITS[0]
+        assert l.mmh_conv2d_wgrad_ws_bytes(by(mk(B, H, W, Cin, Cout, 3, 1, 1, True))) == E.WGRAD_SLOTS[1] * 9 * Cin * Cout * 4
+    finally:
+        assert l.mmh_set_option(key.encode(), old) == 0
+    # the Winograd-domain wgrad GEMM: nine splits off the DMA kernel, two under wino_wgrad_slots = 256
+    P_, T, Cin, Cout = E.WINO_WGRAD_PERSIST
+    assert l.mmh_wino_wgrad_gemm_ws_bytes(T, Cin, Cout, P_) == P_ * 9 * Cin * Cout * 4
+    key, old = restore("wino_wgrad_slots")
+    try:
+        assert l.mmh_set_option(key.encode(), 256) == 0
+        assert l.mmh_wino_wgrad_gemm_ws_bytes(T, Cin, Cout, P_) == P_ * 2 * Cin * Cout * 4
+    finally:
+        assert l.mmh_set_option(key.encode(), old) == 0
+    # the tall stride-2 dgrad is not the halo kernel's
+    B, H, W, Cin, Cout = E.DGRAD_S2_TALL[0]
+    assert l.mmh_dgrad_s2_halo_supported(by(mk(B, H, W, Cin, Cout, 3, 2, 1, False)), Cin) == 0
+    # the 16-bit halo kernel takes the persistent shapes (and folds the second), with more tiles than an MI355X has CUs
+    B, H, W, Cin, Cout, refl = E.HALO_PERSIST_FPROP[0]
+    assert l.mmh_conv3x3_lp16_supported(by(mk(B, H, W, Cin, Cout, 3, 1, 1, refl, L.BF16))) == 1
+    assert B * -(-H // E.HALO_TILE) * -(-W // E.HALO_TILE) * (Cout // E.HALO_TBN) > 256
+    B, H, W, Cin, Cout = E.HALO_PERSIST_DGRAD[0]
+    assert l.mmh_conv3x3_lp16_fold_supported(by(mk(B, H, W, Cin, Cout, 3, 1, 1, True, L.FP16))) == 1
+    assert B * (H // E.HALO_TILE) * (W // E.HALO_TILE) * (Cin // E.HALO_TBN) > 256
+    # pointwise column reductions: B = 1, 81 x 81, C = 96 is cut into 82 chunks of 81 rows - chunk 81 is empty
+    assert l.mmh_norm_stats_ws_bytes(1, 81 * 81, 96) == 82 * 3 * 96 * 4 and 81 * -(-81 * 81 // 82) == 81 * 81
+    assert l.mmh_norm_bwd_ws_bytes(1, 81 * 81, 96) == 82 * 2 * 96 * 4
+    key, old = restore("col_chunks")
+    try:
+        for chunks, want in ((1, 1), (3, 1), (2048, 156)):         # below 16 groups half the knob; at most rows / (8 * 4 rows per pass)
+            assert l.mmh_set_option(key.encode(), chunks) == 0
+            assert l.mmh_colsum_ws_bytes(E.COLSUM[0], E.COLSUM[1]) == want * E.COLSUM[1] * 4, chunks
+    finally:
+        assert l.mmh_set_option(key.encode(), old) == 0
+
+
 def test_mmh_options_environment(built_lib):
     """MMH_OPTIONS=key=value,... reaches mmh_set_option when the library loads; an unknown key stops the run"""
     code = "from mmhand_amd import lib; lib.load(); print('loaded')"

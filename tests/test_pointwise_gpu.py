@@ -12,6 +12,7 @@ from oracle import ops_ref as R
 
 pytestmark = pytest.mark.gpu
 TOL = 2e-5
+GRAD_TOL = 5e-5     # input and affine gradients of the norm (tests/test_pointwise_variants_gpu.py holds its variants to the same)
 G = os.path.join(os.path.dirname(__file__), "golden")
 
 
@@ -42,11 +43,11 @@ def test_norm_act_fwd_bwd(mode, shape, relu, drop, dev):
     ref = R.norm_act(xc, gc, bc, mode, relu, None if mask is None else mask.cpu(), 0.5)
     ref.backward(dy.cpu().double())
     assert R.rel_l1(out, ref) < TOL
-    assert R.rel_l1(x.grad, xc.grad) < 5e-5
+    assert R.rel_l1(x.grad, xc.grad) < GRAD_TOL
     if mode == "batch":
         # with ReLU a handful of elements sit within fp32 rounding of 0 and flip their mask
         # relative to the fp64 oracle; each flip moves a channel sum by O(|dy|)
-        gtol = 5e-4 if relu else 5e-5
+        gtol = 5e-4 if relu else GRAD_TOL
         assert R.rel_l1(gamma.grad, gc.grad) < gtol
         assert R.rel_l1(beta.grad, bc.grad) < gtol
         xn = R.to_nchw(x.detach().cpu())
