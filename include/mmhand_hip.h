@@ -877,6 +877,36 @@ int mmh_decode_inputs_indexed(const void* store, int64_t S, int Hs, int Ws, cons
                               void* x_h1, void* x_h2, void* x_p, void* x_d, void* status,
                               mmh_stream_t s);
 
+/* ---- geometric augmentation inside the decode pass (--augment_geom) ----------------------
+ * an addition: the reference declares --no_flip / --use_flip (options/base_options.py) and
+ * never reads them; its loader (data/generic_dataset.py:133-180) has no spatial augmentation.
+ * mmh_decode_inputs_resized sampling through one inverse affine map per image and side:
+ *   xf  float64 [B,2,6], row-major [a00 a01 a02; a10 a11 a12] per (sample, side); side 0
+ *       samples img1 and dep1, side 1 samples img2 and dep2
+ * The output pixel (x, y) of the Ho x Wo grid reads the source coordinate
+ *   sx = (a00*x + a01*y) + a02,  sy = (a10*x + a11*y) + a12
+ * in float64, each product and sum rounded on its own (no fused multiply-add), clamped to
+ * [0, Ws-1] x [0, Hs-1] before any conversion to an integer (edge replicate; a NaN lands on
+ * 0, no matrix can index outside the image); x0 = min(floor(sx), Ws-1), x1 = min(x0+1, Ws-1),
+ * weight sx - x0, the same in y.  This is F.grid_sample(mode="bilinear",
+ * padding_mode="border", align_corners=True) on pixel coordinates.  Taps, normalisation,
+ * layouts and alignment as mmh_decode_inputs_resized; uv1, uv2 are joints ALREADY transformed
+ * onto the output grid (sigma is not scaled).                                                */
+int mmh_decode_inputs_affine(const void* img1, const void* img2, const void* dep1,
+                             const void* dep2, const void* uv1, const void* uv2,
+                             const void* xf, int B, int Hs, int Ws, int Ho, int Wo,
+                             double sigma, void* x_h1, void* x_h2, void* x_p, void* x_d,
+                             mmh_stream_t s);
+/* The same reading its sources out of a resident store, as mmh_decode_inputs_indexed does:
+ *   uv  float64 [B,2,21,2] per SAMPLE (side 0, side 1), already on the output grid - not the
+ *       per-slot table, the joints change with every epoch's transform
+ *   xf  float64 [B,2,6] as above
+ * Slot guards, status and 64-bit store offsets are mmh_decode_inputs_indexed's.             */
+int mmh_decode_inputs_indexed_affine(const void* store, int64_t S, int Hs, int Ws,
+                                     const void* idx, const void* uv, const void* xf, int B,
+                                     int Ho, int Wo, double sigma, void* x_h1, void* x_h2,
+                                     void* x_p, void* x_d, void* status, mmh_stream_t s);
+
 /* ---- data-parallel gradient all-reduce (apex DistributedDataParallel behind
  * models/MMHandModel.py:109-116; reduce_tensor :381-384) -------------------------
  * The training process already holds ONE RCCL communicator per GPU (torch.distributed's "nccl"

@@ -2044,6 +2044,108 @@ __global__ void decode_inputs_resized_kernel(const uint8_t* __restrict__ img1, c
     }
 }
 
+// The same pass sampling through a per-image, per-side inverse affine map instead of the axis-aligned resize
+// (mmh_decode_inputs_affine; --augment_geom): a = [a00 a01 a02; a10 a11 a12] takes the output pixel (x, y) to the source
+// coordinate sx = (a00 x + a01 y) + a02, sy = (a10 x + a11 y) + a12.  Every product and sum is rounded on its own
+// (contraction off), so the coordinates - and with them taps and weights - are numpy's bit for bit.  Edge replicate: the
+// coordinate is clamped to [0, n - 1] BEFORE it becomes an integer; the comparisons are written so that a NaN lands on 0,
+// and the integer is clamped once more, so no matrix whatever can index outside the image.
+__device__ __forceinline__ void affine_coord(const double* __restrict__ a, int x, int y, double& sx, double& sy) {
+#pragma clang fp contract(off)
+    const double fx = (double)x, fy = (double)y;
+    sx = (a[0] * fx + a[1] * fy) + a[2];
+    sy = (a[3] * fx + a[4] * fy) + a[5];
+}
+__device__ __forceinline__ ResizeTap affine_tap(double s, int n_src) {
+    const double hi = (double)(n_src - 1);
+    s = s > 0.0 ? s : 0.0;                   // NaN compares false: 0
+    s = s < hi ? s : hi;
+    ResizeTap t;
+    t.i0 = max(0, min((int)s, n_src - 1));   // 0 <= s <= n - 1: the cast is the floor
+    t.i1 = min(t.i0 + 1, n_src - 1);
+    t.w = s - (double)t.i0;
+    return t;
+}
+struct AffineTaps { int64_t o00, o01, o10, o11; double wx, wy; };
+__device__ __forceinline__ AffineTaps affine_taps(const double* __restrict__ a, int x, int y, int Hs, int Ws) {
+    double sx, sy;
+    affine_coord(a, x, y, sx, sy);
+    const ResizeTap tx = affine_tap(sx, Ws), ty = affine_tap(sy, Hs);
+    const int64_t row0 = (int64_t)ty.i0 * Ws, row1 = (int64_t)ty.i1 * Ws;
+    AffineTaps t;
+    t.o00 = (row0 + tx.i0) * 3, t.o01 = (row0 + tx.i1) * 3, t.o10 = (row1 + tx.i0) * 3, t.o11 = (row1 + tx.i1) * 3;
+    t.wx = tx.w, t.wy = ty.w;
+    return t;
+}
+__device__ __forceinline__ float depth_affine(const uint8_t* __restrict__ dep, const AffineTaps& t) {
+    return depth_f64(lerp2(depth_raw(dep + t.o00), depth_raw(dep + t.o01), depth_raw(dep + t.o10), depth_raw(dep + t.o11),
+                           t.wx, t.wy));
+}
+// decode_lane with the sampling map of the sample's two sides, xf = float64 [2][6]: side 0 samples img1 and dep1, side 1
+// img2 and dep2.  Lane layout, outputs, tap combination and pose-map lanes are decode_lane's (the joints arrive transformed).
+__device__ __forceinline__ void decode_lane_affine(const uint8_t* __restrict__ img1, const uint8_t* __restrict__ img2,
+                                                   const uint8_t* __restrict__ dep1, const uint8_t* __restrict__ dep2,
+                                                   const double* __restrict__ u1, const double* __restrict__ u2,
+                                                   const double* __restrict__ xf, int q, int64_t px, int x, int y,
+                                                   int Hs, int Ws, double sigma,
+                                                   float* __restrict__ xh1, float* __restrict__ xh2,
+                                                   float* __restrict__ xp, float* __restrict__ xd) {
+    if (q >= 4) {
+        // pose maps: channels 4 (q - 4) .. + 3 of 44 (P1 in 0..20, P2 in 21..41, 42 and 43 zero)
+        float v[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int c = (q - 4) * 4 + e;
+            v[e] = c < 21 ? heat((double)x, (double)y, u1[2 * c], u1[2 * c + 1], sigma)
+                 : c < 42 ? heat((double)x, (double)y, u2[2 * (c - 21)], u2[2 * (c - 21) + 1], sigma) : 0.f;
+        }
+        st4(xp, px * 11 + (q - 4), make_float4(v[0], v[1], v[2], v[3]));
+        return;
+    }
+    if (q < 2) {
+        // images: BGR uint8 -> RGB normalised
+        const AffineTaps t = affine_taps(xf + 6 * q, x, y, Hs, Ws);
+        const uint8_t* p = q == 0 ? img1 : img2;
+        float c[3];
+#pragma unroll
+        for (int e = 0; e < 3; ++e)
+            c[e] = norm_f64(lerp2((double)p[t.o00 + e], (double)p[t.o01 + e], (double)p[t.o10 + e], (double)p[t.o11 + e],
+                                  t.wx, t.wy));
+        st4(q == 0 ? xh1 : xh2, px, make_float4(c[2], c[1], c[0], 0.f));
+    } else {
+        // depth: 256*G + R per tap (BGR order: index 1 = G, 2 = R), interpolated, then / 700 and normalised
+        const float d2 = depth_affine(dep2, affine_taps(xf + 6, x, y, Hs, Ws));
+        if (q == 2) {
+            const float d1 = depth_affine(dep1, affine_taps(xf, x, y, Hs, Ws));
+            st4(xd, px * 2, make_float4(d1, d1, d1, d2));
+        } else {
+            st4(xd, px * 2 + 1, make_float4(d2, d2, 0.f, 0.f));
+        }
+    }
+}
+
+__global__ void decode_inputs_affine_kernel(const uint8_t* __restrict__ img1, const uint8_t* __restrict__ img2,
+                                            const uint8_t* __restrict__ dep1, const uint8_t* __restrict__ dep2,
+                                            const double* __restrict__ uv1, const double* __restrict__ uv2,
+                                            const double* __restrict__ xf, int B, int Hs, int Ws, int Ho, int Wo,
+                                            double sigma, float* __restrict__ xh1, float* __restrict__ xh2,
+                                            float* __restrict__ xp, float* __restrict__ xd) {
+    const int64_t total = (int64_t)B * Ho * Wo * DECODE_LANES;
+    const int64_t img_bytes = (int64_t)Hs * Ws * 3;
+    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (; i < total; i += stride) {
+        const int q = (int)(i % DECODE_LANES);
+        const int64_t px = i / DECODE_LANES;
+        const int x = (int)(px % Wo);
+        const int64_t t = px / Wo;
+        const int y = (int)(t % Ho);
+        const int64_t b = t / Ho;
+        decode_lane_affine(img1 + b * img_bytes, img2 + b * img_bytes, dep1 + b * img_bytes, dep2 + b * img_bytes,
+                           uv1 + b * 42, uv2 + b * 42, xf + b * 12, q, px, x, y, Hs, Ws, sigma, xh1, xh2, xp, xd);
+    }
+}
+
 // ------------------------------------------------------------------ resident dataset
 // The decoded dataset stays in device memory as uint8 [S,Hs,Ws,3]; a batch is a row of slots.  Slots come from a table, so
 // both kernels guard them with plain branches: a bad row costs its sample (zeros / nothing written) and a status bit, never
@@ -2098,6 +2200,40 @@ __global__ void decode_inputs_indexed_kernel(const uint8_t* __restrict__ store, 
         }
         decode_lane(store + s0 * img_bytes, store + s1 * img_bytes, store + s2 * img_bytes, store + s3 * img_bytes,
                     uvt + s0 * 42, uvt + s1 * 42, q, px, x, y, Hs, Ws, Ho, Wo, sigma, xh1, xh2, xp, xd);
+    }
+}
+
+// decode_inputs_affine_kernel with the four sources looked up by slot (--resident_dataset --augment_geom).  The joints are
+// the SAMPLE's, uv = float64 [B,2,21,2] (they change with every epoch's transform), not rows of a per-slot table; the slot
+// guards are decode_inputs_indexed_kernel's.
+__global__ void decode_inputs_indexed_affine_kernel(const uint8_t* __restrict__ store, int64_t S, int Hs, int Ws,
+                                                    const int* __restrict__ idx, const double* __restrict__ uv,
+                                                    const double* __restrict__ xf, int B, int Ho, int Wo, double sigma,
+                                                    float* __restrict__ xh1, float* __restrict__ xh2,
+                                                    float* __restrict__ xp, float* __restrict__ xd,
+                                                    int* __restrict__ status) {
+    const int64_t total = (int64_t)B * Ho * Wo * DECODE_LANES;
+    const int64_t img_bytes = (int64_t)Hs * Ws * 3;
+    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (; i < total; i += stride) {
+        const int q = (int)(i % DECODE_LANES);
+        const int64_t px = i / DECODE_LANES;
+        const int x = (int)(px % Wo);
+        const int64_t t = px / Wo;
+        const int y = (int)(t % Ho);
+        const int64_t b = t / Ho;
+        const int64_t s0 = idx[b * 4], s1 = idx[b * 4 + 1], s2 = idx[b * 4 + 2], s3 = idx[b * 4 + 3];
+        if (s0 < 0 || s0 >= S || s1 < 0 || s1 >= S || s2 < 0 || s2 >= S || s3 < 0 || s3 >= S) {
+            const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (q >= 4) st4(xp, px * 11 + (q - 4), z);
+            else if (q >= 2) st4(xd, px * 2 + (q - 2), z);
+            else st4(q == 0 ? xh1 : xh2, px, z);
+            if (status && q == 0 && x == 0 && y == 0) atomicOr(status, 1);
+            continue;
+        }
+        decode_lane_affine(store + s0 * img_bytes, store + s1 * img_bytes, store + s2 * img_bytes, store + s3 * img_bytes,
+                           uv + b * 84, uv + b * 84 + 42, xf + b * 12, q, px, x, y, Hs, Ws, sigma, xh1, xh2, xp, xd);
     }
 }
 
@@ -3118,6 +3254,44 @@ int mmh_decode_inputs_indexed(const void* store, int64_t S, int Hs, int Ws, cons
                        static_cast<float*>(x_h2), static_cast<float*>(x_p), static_cast<float*>(x_d),
                        static_cast<int*>(status));
     return mmh::check_launch("decode_inputs_indexed");
+}
+
+int mmh_decode_inputs_affine(const void* img1, const void* img2, const void* dep1, const void* dep2,
+                             const void* uv1, const void* uv2, const void* xf, int B, int Hs, int Ws, int Ho, int Wo,
+                             double sigma, void* x_h1, void* x_h2, void* x_p, void* x_d, mmh_stream_t s) {
+    MMH_REQUIRE(img1 && img2 && dep1 && dep2 && uv1 && uv2 && xf && x_h1 && x_h2 && x_p && x_d,
+                "mmh_decode_inputs_affine: NULL buffer");
+    MMH_REQUIRE(B > 0 && Hs > 0 && Ws > 0 && Ho > 0 && Wo > 0 && sigma > 0, "mmh_decode_inputs_affine: bad shape");
+    MMH_REQUIRE(((reinterpret_cast<uintptr_t>(x_h1) | reinterpret_cast<uintptr_t>(x_h2) | reinterpret_cast<uintptr_t>(x_p) |
+                  reinterpret_cast<uintptr_t>(x_d)) & 15) == 0, "mmh_decode_inputs_affine: outputs must be 16-byte aligned");
+    MMH_REQUIRE((reinterpret_cast<uintptr_t>(xf) & 7) == 0, "mmh_decode_inputs_affine: xf must be 8-byte aligned");
+    hipLaunchKernelGGL(decode_inputs_affine_kernel, dim3(grid_for((int64_t)B * Ho * Wo * DECODE_LANES)), dim3(TPB), 0,
+                       mmh::as_stream(s), static_cast<const uint8_t*>(img1),
+                       static_cast<const uint8_t*>(img2), static_cast<const uint8_t*>(dep1),
+                       static_cast<const uint8_t*>(dep2), static_cast<const double*>(uv1),
+                       static_cast<const double*>(uv2), static_cast<const double*>(xf), B, Hs, Ws, Ho, Wo, sigma,
+                       static_cast<float*>(x_h1), static_cast<float*>(x_h2), static_cast<float*>(x_p),
+                       static_cast<float*>(x_d));
+    return mmh::check_launch("decode_inputs_affine");
+}
+
+int mmh_decode_inputs_indexed_affine(const void* store, int64_t S, int Hs, int Ws, const void* idx, const void* uv,
+                                     const void* xf, int B, int Ho, int Wo, double sigma, void* x_h1, void* x_h2, void* x_p,
+                                     void* x_d, void* status, mmh_stream_t s) {
+    MMH_REQUIRE(store && idx && uv && xf && x_h1 && x_h2 && x_p && x_d, "mmh_decode_inputs_indexed_affine: NULL buffer");
+    MMH_REQUIRE(B > 0 && Hs > 0 && Ws > 0 && Ho > 0 && Wo > 0 && sigma > 0, "mmh_decode_inputs_indexed_affine: bad shape");
+    MMH_REQUIRE(S >= 1, "mmh_decode_inputs_indexed_affine: S must be at least 1");
+    MMH_REQUIRE(((reinterpret_cast<uintptr_t>(x_h1) | reinterpret_cast<uintptr_t>(x_h2) | reinterpret_cast<uintptr_t>(x_p) |
+                  reinterpret_cast<uintptr_t>(x_d)) & 15) == 0,
+                "mmh_decode_inputs_indexed_affine: outputs must be 16-byte aligned");
+    MMH_REQUIRE(((reinterpret_cast<uintptr_t>(xf) | reinterpret_cast<uintptr_t>(uv)) & 7) == 0,
+                "mmh_decode_inputs_indexed_affine: uv and xf must be 8-byte aligned");
+    hipLaunchKernelGGL(decode_inputs_indexed_affine_kernel, dim3(grid_for((int64_t)B * Ho * Wo * DECODE_LANES)), dim3(TPB), 0,
+                       mmh::as_stream(s), static_cast<const uint8_t*>(store), S, Hs, Ws, static_cast<const int*>(idx),
+                       static_cast<const double*>(uv), static_cast<const double*>(xf), B, Ho, Wo, sigma,
+                       static_cast<float*>(x_h1), static_cast<float*>(x_h2), static_cast<float*>(x_p),
+                       static_cast<float*>(x_d), static_cast<int*>(status));
+    return mmh::check_launch("decode_inputs_indexed_affine");
 }
 
 int mmh_prep_weights_bf16(const void* w, int taps, int Cin, int Cout, void* w_plain, void* w_t,

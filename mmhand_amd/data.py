@@ -25,7 +25,14 @@ batch is a row of slots and ONE kernel (mmh_decode_inputs_indexed) - no file rea
 
 `HandFolderLoader` with `opt.pairing` = curriculum | nearest (--pairing; the default `random` is the reference's live loader):
 the paper's two pairing strategies on the reference's pose distance (nearest_neighbor_search.py:68-83, on the device:
-ops.pose_features / pose_knn / pose_pair_distance).  Both are decided once, in the constructor, so the order stays static."""
+ops.pose_features / pose_knn / pose_pair_distance).  Both are decided once, in the constructor, so the order stays static.
+
+`HandFolderLoader` with `opt.augment_geom` (--augment_geom; off by default): every image gets a random rotation, scale, shift
+(and flip) per epoch.  The host draws the parameters for the whole dataset from (aug_seed, epoch) (`augment_draws`), builds
+the 2x3 sampling matrices and transforms the joints in float64 (`affine_forward`, `affine_inverse`, `affine_joints`); the
+device samples through the matrix inside its decode pass (mmh_decode_inputs_affine / mmh_decode_inputs_indexed_affine).  The
+order of the batches, and with it the resident store, stays what it is: only `set_epoch`'s number reaches the draws."""
+import math
 import os
 import pickle
 import random
@@ -34,7 +41,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .options import check_resize_inputs
+from .options import check_augment, check_resize_inputs
 
 
 class SyntheticHandLoader:
@@ -217,13 +224,105 @@ def check_pairing(opt):
     return pairing, pool
 
 
+# ----------------------------------------------------------------------------- geometric augmentation: host-side maths
+# THE place the matrices of --augment_geom are built (as ops.resize_joints is for the resize): float64 numpy, every
+# function broadcasting over leading dimensions.  Conventions: a point is (u, v) = (x, y) in pixels; a 2x3 matrix
+# [m00 m01 m02; m10 m11 m12] acts as u' = m00 u + m01 v + m02, v' = m10 u + m11 v + m12.
+def _cos_sin_deg(theta_deg):
+    """cos and sin of degrees, one libm call per element (an array routine may round differently from a scalar one, and a
+    batch must get the matrix a whole epoch's table gets); multiples of 90 degrees are exact"""
+    t = np.asarray(theta_deg, dtype=np.float64)
+    c, s = np.empty(t.shape, np.float64), np.empty(t.shape, np.float64)
+    exact = {0.0: (1.0, 0.0), 90.0: (0.0, 1.0), 180.0: (-1.0, 0.0), 270.0: (0.0, -1.0)}
+    for i, d in np.ndenumerate(t):
+        d = float(d)
+        c[i], s[i] = exact.get(math.fmod(d, 360.0) % 360.0) or (math.cos(math.radians(d)), math.sin(math.radians(d)))
+    return c, s
+
+
+def affine_forward(theta_deg, scale, tx, ty, flip, src):
+    """Forward map of one draw on the Hs x Ws source grid, float64 [..., 2, 3]: p' = c + t + s R(theta) F (p - c) with the
+    centre c = ((Ws - 1) / 2, (Hs - 1) / 2), the shift t = (tx Ws, ty Hs) and F = diag(-1, 1) where `flip` is set."""
+    Hs, Ws = int(src[0]), int(src[1])
+    theta_deg, scale, tx, ty, flip = np.broadcast_arrays(*(np.asarray(a, dtype=np.float64) for a in (theta_deg, scale, tx, ty, flip)))
+    cos, sin = _cos_sin_deg(theta_deg)
+    f = np.where(flip != 0, -1.0, 1.0)
+    m = np.empty(theta_deg.shape + (2, 3), np.float64)
+    m[..., 0, 0], m[..., 0, 1] = scale * cos * f, -(scale * sin)
+    m[..., 1, 0], m[..., 1, 1] = scale * sin * f, scale * cos
+    cx, cy = (Ws - 1) / 2.0, (Hs - 1) / 2.0
+    m[..., 0, 2] = cx + tx * Ws - (m[..., 0, 0] * cx + m[..., 0, 1] * cy)
+    m[..., 1, 2] = cy + ty * Hs - (m[..., 1, 0] * cx + m[..., 1, 1] * cy)
+    return m
+
+
+def affine_inverse(fwd, src, dst=None):
+    """The sampling matrix the kernels take, float64 [..., 2, 3]: output pixel (x, y) of the Ho x Wo grid -> source coordinate
+    on the Hs x Ws grid = the inverse of (`fwd`, then the resize map u' = (u + 0.5) Wo / Ws - 0.5 of ops.resize_joints).
+    Closed form on the 2x2 part; non-finite entries and a zero determinant are refused."""
+    (Hs, Ws), (Ho, Wo) = (int(src[0]), int(src[1])), ((int(dst[0]), int(dst[1])) if dst is not None else (int(src[0]), int(src[1])))
+    fwd = np.asarray(fwd, dtype=np.float64)
+    if fwd.shape[-2:] != (2, 3):
+        raise ValueError(f"affine_inverse: [..., 2, 3] expected, got {fwd.shape}")
+    if not np.isfinite(fwd).all():
+        raise ValueError("affine_inverse: a matrix with a non-finite entry")
+    det = fwd[..., 0, 0] * fwd[..., 1, 1] - fwd[..., 0, 1] * fwd[..., 1, 0]
+    if (det == 0.0).any() or not np.isfinite(1.0 / det).all():
+        raise ValueError("affine_inverse: a singular matrix (determinant 0)")
+    i00, i01, i10, i11 = fwd[..., 1, 1] / det, -fwd[..., 0, 1] / det, -fwd[..., 1, 0] / det, fwd[..., 0, 0] / det
+    kx, ky = float(Ws) / float(Wo), float(Hs) / float(Ho)
+    dx, dy = (0.5 * kx - 0.5) - fwd[..., 0, 2], (0.5 * ky - 0.5) - fwd[..., 1, 2]
+    a = np.empty(fwd.shape, np.float64)
+    a[..., 0, 0], a[..., 0, 1], a[..., 0, 2] = i00 * kx, i01 * ky, i00 * dx + i01 * dy
+    a[..., 1, 0], a[..., 1, 1], a[..., 1, 2] = i10 * kx, i11 * ky, i10 * dx + i11 * dy
+    if not np.isfinite(a).all():
+        raise ValueError("affine_inverse: the inverse has a non-finite entry")
+    return a
+
+
+def affine_joints(uv, fwd, src, dst=None):
+    """Joints [..., 21, 2 or 3] = (u, v[, depth]) of the source image on the output grid: through `fwd` ([2,3], or
+    [..., 2, 3] with the joints' leading dimensions), then the resize map of ops.resize_joints; depth unchanged.  numpy in,
+    numpy out, float64."""
+    (Hs, Ws), (Ho, Wo) = (int(src[0]), int(src[1])), ((int(dst[0]), int(dst[1])) if dst is not None else (int(src[0]), int(src[1])))
+    out = np.array(uv, dtype=np.float64, copy=True)
+    m = np.asarray(fwd, dtype=np.float64)[..., None, :, :]          # one matrix for the 21 joints of an image
+    u, v = out[..., 0].copy(), out[..., 1].copy()
+    pu = (m[..., 0, 0] * u + m[..., 0, 1] * v) + m[..., 0, 2]
+    pv = (m[..., 1, 0] * u + m[..., 1, 1] * v) + m[..., 1, 2]
+    out[..., 0] = (pu + 0.5) * float(Wo) / float(Ws) - 0.5
+    out[..., 1] = (pv + 0.5) * float(Ho) / float(Hs) - 0.5
+    return out
+
+
+def augment_draws(n_items, epoch, opt):
+    """The draws of one epoch for the WHOLE dataset, float64 [n_items, 2, 5] = (theta in degrees, scale, tx, ty, flip) per item
+    and side (0 = source, 1 = target), from one np.random.default_rng([aug_seed, epoch]).  Indexed by dataset item, so what an
+    item gets in an epoch depends on nothing else - batch size, rank, world size, file or store.  --aug_pair shared: side 1
+    is side 0."""
+    rotate, scale, shift, flip, pair, seed = check_augment(opt)
+    u = np.random.default_rng([int(seed), int(epoch)]).random((int(n_items), 2, 5))
+    d = np.empty_like(u)
+    d[..., 0] = (2.0 * u[..., 0] - 1.0) * rotate
+    d[..., 1] = 1.0 + (2.0 * u[..., 1] - 1.0) * scale
+    d[..., 2] = (2.0 * u[..., 2] - 1.0) * shift
+    d[..., 3] = (2.0 * u[..., 3] - 1.0) * shift
+    d[..., 4] = u[..., 4] < flip
+    if pair == "shared":
+        d[:, 1] = d[:, 0]
+    return d
+
+
 class ResidentBatch:
     """One batch of a resident store: `idx` int32 [B,4] (a row block of the loader's device table) names the slots of
     (img1, img2, dep1, dep2) in `store` uint8 [S,Hs,Ws,3]; `uv_table` float64 [S,21,2] holds every slot's joints on the grid
-    of `out_size` (the loader's --resize_inputs; None = the store's size).  ops.decode_inputs_indexed consumes it as it is."""
+    of `out_size` (the loader's --resize_inputs; None = the store's size).  ops.decode_inputs_indexed consumes it as it is.
+    --augment_geom: `xf` float64 [B,2,6] and `uv` float64 [B,2,21,2] - row blocks of the epoch's tables - replace `uv_table`
+    (ops.decode_inputs_indexed_affine)."""
 
-    def __init__(self, store, idx, uv_table, out_size=None):
+    def __init__(self, store, idx, uv_table, out_size=None, xf=None, uv=None):
         self.store, self.idx, self.uv_table, self.out_size = store, idx, uv_table, out_size
+        self.xf, self.uv = xf, uv
         self.B = int(idx.shape[0])
 
     def gather(self):
@@ -289,6 +388,13 @@ class HandFolderLoader:
         # random mode computed on first access only; `pairing_fallbacks` = the targets `nearest` found no neighbour for
         self.pairing_fallbacks = []
         self._pair_distance = None
+        # --augment_geom: the validated ranges (None = off), the epoch number of the draws (set_epoch; nothing else reads it)
+        # and the dataset item of every loader position - the target's place in the split's sorted list, which the curriculum's
+        # reordering carries along, so an item's transform does not depend on the pairing order
+        self.augment = check_augment(opt)
+        self.aug_epoch = 0
+        self.aug_item = np.arange(len(self.image_target), dtype=np.int64)
+        self._aug_draws = None
         if self.pairing != "random":
             self._pair(data, 0.0 if ratio is None else float(ratio))
         self.decoded = decoded
@@ -360,6 +466,7 @@ class HandFolderLoader:
             order = curriculum_order(d)
             self.image_source = [self.image_source[i] for i in order]
             self.image_target = [self.image_target[i] for i in order]
+            self.aug_item = self.aug_item[order]
             self._pair_distance = d[order]
             return
         if self.match_pool == "train":
@@ -390,7 +497,26 @@ class HandFolderLoader:
         return self.annotations[folder][name]
 
     def set_epoch(self, epoch):
-        """kept for the training loop's interface; the reference's sampler stays at epoch 0 (see the class docstring)"""
+        """the epoch number of --augment_geom's draws, and nothing else: the reference's sampler stays at epoch 0 (see the
+        class docstring), so indices() - and with it the order, the pairs and the resident store - does not see it"""
+        self.aug_epoch = int(epoch)
+
+    # ------------------------------------------------------------------ geometric augmentation
+    def _draws(self):
+        """this epoch's draws for the whole dataset, computed once per epoch number"""
+        if self._aug_draws is None or self._aug_draws[0] != self.aug_epoch:
+            self._aug_draws = (self.aug_epoch, augment_draws(len(self.image_target), self.aug_epoch, self.opt))
+        return self._aug_draws[1]
+
+    def _augment_rows(self, items, uv, c, src):
+        """items: loader positions [n]; uv float64 [n,2,21,2] and c [n,2,21,3]: the joints of each position's (source, target)
+        at the files' size src = (Hs, Ws) -> (xf [n,2,6] for the kernels, uv and c on the output grid).  One batch or a whole
+        epoch's table: the same arithmetic per element, so the two agree bit for bit."""
+        d = self._draws()[self.aug_item[np.asarray(items, dtype=np.int64)]]
+        fwd = affine_forward(d[..., 0], d[..., 1], d[..., 2], d[..., 3], d[..., 4], src)
+        dst = ops.resize_size(self.out_size, src) or src
+        xf = affine_inverse(fwd, src, dst).reshape(len(d), 2, 6)
+        return np.ascontiguousarray(xf), affine_joints(uv, fwd, src, dst), affine_joints(c, fwd, src, dst)
 
     def indices(self):
         n = len(self.image_source)
@@ -424,6 +550,8 @@ class HandFolderLoader:
         uv2 = np.asarray(a2["uv_coord"], dtype=np.float64).reshape(21, 2)
         z1 = np.expand_dims(np.asarray(a1["depth"], dtype=np.float64), -1) / 700.0 * 255
         z2 = np.expand_dims(np.asarray(a2["depth"], dtype=np.float64), -1) / 700.0 * 255
+        if self.augment is not None:
+            return self._load_augmented(item, h_1, h_2, uv1, uv2, np.concatenate([uv1, z1], axis=-1), np.concatenate([uv2, z2], axis=-1))
         if self.device_png:
             return dict(img1=_read_bytes(h_1), img2=_read_bytes(h_2), dep1=_read_bytes(h_1.replace("color", "depth")),
                         dep2=_read_bytes(h_2.replace("color", "depth")), uv1=uv1, uv2=uv2,
@@ -431,6 +559,19 @@ class HandFolderLoader:
         return dict(img1=_read_bgr(h_1), img2=_read_bgr(h_2), dep1=_read_bgr(h_1.replace("color", "depth")),
                     dep2=_read_bgr(h_2.replace("color", "depth")), uv1=uv1, uv2=uv2,
                     C1=np.concatenate([uv1, z1], axis=-1), C2=np.concatenate([uv2, z2], axis=-1), H1_path=h_1, H2_path=h_2)
+
+    def _load_augmented(self, item, h_1, h_2, uv1, uv2, c1, c2):
+        """load_sample under --augment_geom: the same files, untouched; the sample's two sampling matrices ride along as `xf`
+        [2,6] and uv1 / uv2 / C1 / C2 leave already transformed, on the output grid"""
+        read = _read_bytes if self.device_png else _read_bgr
+        s = dict(img1=read(h_1), img2=read(h_2), dep1=read(h_1.replace("color", "depth")),
+                 dep2=read(h_2.replace("color", "depth")), H1_path=h_1, H2_path=h_2)
+        src = png_size(h_1) if self.device_png else s["img1"].shape[:2]
+        if src is None:
+            raise ValueError(f"--augment_geom --device_png: {h_1} is not a PNG file, its size is unknown before the decode")
+        xf, uv, c = self._augment_rows([item], np.stack([uv1, uv2])[None], np.stack([c1, c2])[None], src)
+        s.update(xf=xf[0], uv1=uv[0, 0], uv2=uv[0, 1], C1=c[0, 0], C2=c[0, 1])
+        return s
 
     def _collate(self, samples):
         out = {}
@@ -441,7 +582,8 @@ class HandFolderLoader:
             dec = self._png_sets[self._png_turn % 2]
             self._png_turn += 1
             out["_png"] = (dec, dec.pack([s[k] for k in _IMAGE_KEYS for s in samples]))
-        for k in ("uv1", "uv2", "C1", "C2") if self.device_png else ("img1", "img2", "dep1", "dep2", "uv1", "uv2", "C1", "C2"):
+        keys = ("uv1", "uv2", "C1", "C2") if self.device_png else ("img1", "img2", "dep1", "dep2", "uv1", "uv2", "C1", "C2")
+        for k in keys + (("xf",) if self.augment is not None else ()):
             t = torch.from_numpy(np.stack([s[k] for s in samples]))
             out[k] = t.pin_memory() if torch.cuda.is_available() else t
         out["H1_path"] = [s["H1_path"] for s in samples]
@@ -457,6 +599,8 @@ class HandFolderLoader:
             groups = [groups[g] for g in only]
         if not groups:
             return
+        if self.augment is not None:
+            self._draws()                   # once, here: not by whichever worker thread asks first
         with ThreadPoolExecutor(max_workers=max(1, self.threads)) as pool:
             nxt = [pool.submit(self.load_sample, i) for i in groups[0]]
             for gi in range(len(groups)):
@@ -494,9 +638,14 @@ class HandFolderLoader:
             return out
         src = tuple(out["img1"].shape[1:3])
         dst = ops.resize_size(self.out_size, src)
-        xh1, xh2, xp, xd = ops.decode_inputs(out["img1"], out["img2"], out["dep1"], out["dep2"], out["uv1"], out["uv2"],
-                                             out_size=dst)
-        c1, c2 = (out[k] if dst is None else ops.resize_joints(out[k], src, dst) for k in ("C1", "C2"))
+        if "xf" in out:                     # --augment_geom: joints and C arrive transformed, on the output grid
+            xh1, xh2, xp, xd = ops.decode_inputs_affine(out["img1"], out["img2"], out["dep1"], out["dep2"], out["uv1"],
+                                                        out["uv2"], out["xf"], out_size=dst)
+            c1, c2 = out["C1"], out["C2"]
+        else:
+            xh1, xh2, xp, xd = ops.decode_inputs(out["img1"], out["img2"], out["dep1"], out["dep2"], out["uv1"], out["uv2"],
+                                                 out_size=dst)
+            c1, c2 = (out[k] if dst is None else ops.resize_joints(out[k], src, dst) for k in ("C1", "C2"))
         v = ops.nhwc_to_nchw_view
         return {"H1": v(xh1, 3), "H2": v(xh2, 3), "P1": v(xp)[:, :21], "P2": v(xp)[:, 21:42], "D1": v(xd)[:, :3],
                 "D2": v(xd)[:, 3:6], "C1": c1, "C2": c2, "H1_path": out["H1_path"], "H2_path": out["H2_path"]}
@@ -528,14 +677,30 @@ class HandFolderLoader:
                 a = self.get_labels(path)
                 uv[slot] = np.asarray(a["uv_coord"], dtype=np.float64).reshape(21, 2)
                 c[slot] = np.concatenate([uv[slot], np.expand_dims(np.asarray(a["depth"], dtype=np.float64), -1) / 700.0 * 255], -1)
+        uv0, c0 = uv, c                                 # at the files' size, on the host: what --augment_geom transforms per epoch
         uv, c = torch.from_numpy(uv).to(dev), torch.from_numpy(c).to(dev)
         dst = ops.resize_size(self.out_size, size)
         if dst is not None:                             # joints are scaled in ONE place, once
             uv, c = ops.resize_joints(uv, size, dst), ops.resize_joints(c, size, dst)
         self._res = dict(paths=paths, table=table, lengths=table_lengths(table), filled=np.zeros(S, dtype=bool), size=size,
                          store=torch.empty((S, Hs, Ws, 3), dtype=torch.uint8, device=dev), uv=uv.contiguous(),
-                         c=c.contiguous(), table_dev=torch.from_numpy(table).to(dev))
+                         c=c.contiguous(), table_dev=torch.from_numpy(table).to(dev), uv0=uv0, c0=c0, aug=None)
         self.resident_state = f"on: {S} images of {Hs} x {Ws}, {need} bytes"
+
+    def _resident_epoch_tables(self):
+        """--augment_geom on the resident path, at the top of an epoch: the epoch's xf [N,2,6], uv [N,2,21,2] and c [N,2,21,3]
+        for this rank's N samples in loader order, built on the host and uploaded once; batch g is rows first[g] .. + its
+        length, so serving it stays one kernel and no upload"""
+        r = self._res
+        if r["aug"] is not None and r["aug"]["epoch"] == self.aug_epoch:
+            return
+        groups = _batch_groups(self.indices(), self.opt.batchSize, self.opt.max_dataset_size)
+        items = np.array([i for g in groups for i in g], dtype=np.int64)
+        rows = np.concatenate([r["table"][g, :n] for g, n in enumerate(r["lengths"])])          # [N,4] slots
+        xf, uv, c = self._augment_rows(items, r["uv0"][rows[:, :2]], r["c0"][rows[:, :2]], r["size"])
+        first = np.concatenate([[0], np.cumsum(r["lengths"])]).astype(np.int64)
+        t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.device)                  # noqa: E731
+        r["aug"] = dict(epoch=self.aug_epoch, xf=t(xf), uv=t(uv), c=t(c), first=first)
 
     def _batch_is_resident(self, g):
         r = self._res
@@ -568,12 +733,21 @@ class HandFolderLoader:
         r = self._res
         n = r["lengths"][g]
         idx = r["table_dev"][g, :n]
-        c1, c2 = r["c"][idx[:, 0].long()], r["c"][idx[:, 1].long()]
         p1, p2 = ([r["paths"][s] for s in r["table"][g, :n, j]] for j in (0, 1))
-        rb = ResidentBatch(r["store"], idx, r["uv"], self.out_size)
+        if self.augment is not None:
+            a = r["aug"]
+            o = int(a["first"][g])
+            c1, c2 = a["c"][o:o + n, 0], a["c"][o:o + n, 1]
+            rb = ResidentBatch(r["store"], idx, r["uv"], self.out_size, xf=a["xf"][o:o + n], uv=a["uv"][o:o + n])
+        else:
+            c1, c2 = r["c"][idx[:, 0].long()], r["c"][idx[:, 1].long()]
+            rb = ResidentBatch(r["store"], idx, r["uv"], self.out_size)
         if not self.decoded:
             return {"resident": rb, "C1": c1, "C2": c2, "H1_path": p1, "H2_path": p2}
-        xh1, xh2, xp, xd = ops.decode_inputs_indexed(rb.store, rb.idx, rb.uv_table, out_size=rb.out_size)
+        if rb.xf is not None:
+            xh1, xh2, xp, xd = ops.decode_inputs_indexed_affine(rb.store, rb.idx, rb.uv, rb.xf, out_size=rb.out_size)
+        else:
+            xh1, xh2, xp, xd = ops.decode_inputs_indexed(rb.store, rb.idx, rb.uv_table, out_size=rb.out_size)
         v = ops.nhwc_to_nchw_view
         return {"H1": v(xh1, 3), "H2": v(xh2, 3), "P1": v(xp)[:, :21], "P2": v(xp)[:, 21:42], "D1": v(xd)[:, :3],
                 "D2": v(xd)[:, 3:6], "C1": c1, "C2": c2, "H1_path": p1, "H2_path": p2}
@@ -587,6 +761,8 @@ class HandFolderLoader:
         # path unchanged and fill it on their way
         n_batches = len(self._res["lengths"])
         todo = [g for g in range(n_batches) if not self._batch_is_resident(g)]
+        if self.augment is not None and len(todo) < n_batches:
+            self._resident_epoch_tables()
         from_files = self.host_batches(only=todo)
         todo = set(todo)
         try:

@@ -193,6 +193,8 @@ SIGNATURES = {
     "mmh_decode_inputs_resized": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _d, _vp, _vp, _vp, _vp, _vp]),
     "mmh_store_images": (_i, [_vp, _vp, _i, _i, _i, _vp, _i64, _vp, _vp]),
     "mmh_decode_inputs_indexed": (_i, [_vp, _i64, _i, _i, _vp, _vp, _i, _i, _i, _d, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mmh_decode_inputs_affine": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _d, _vp, _vp, _vp, _vp, _vp]),
+    "mmh_decode_inputs_indexed_affine": (_i, [_vp, _i64, _i, _i, _vp, _vp, _vp, _i, _i, _i, _d, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mmh_rccl_bind": (_i, [C.c_char_p]),
     "mmh_rccl_comm_ranks": (_i, [_vp]),
     "mmh_allreduce_bucket": (_i, [_vp, _vp, _i64, _i, _vp]),

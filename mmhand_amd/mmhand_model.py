@@ -526,7 +526,10 @@ class MMHandModel(torch.nn.Module):
         dev = self.device
         if "img1" in input:
             # a RAW batch of data.HandFolderLoader (uint8 images / depth PNGs, float64 joints): decoded on the device
-            raw = ("img1", "img2", "dep1", "dep2", "uv1", "uv2")
+            # --augment_geom: the loader's sampling matrices ride along as "xf"; uv1 / uv2 / C1 / C2 are then already transformed
+            # and on the output grid, so nothing is scaled here
+            aug = "xf" in input
+            raw = ("img1", "img2", "dep1", "dep2", "uv1", "uv2") + (("xf",) if aug else ())
             if any(not input[k].is_cuda for k in raw):
                 if getattr(self, "_copy_stream", None) is None:
                     self._copy_stream = torch.cuda.Stream(dev)
@@ -541,9 +544,13 @@ class MMHandModel(torch.nn.Module):
             if "C1" in input and "C2" in input:
                 # (u, v, depth) of the joints on the grid the networks see: scaled with the images under --resize_inputs
                 src, dst = tuple(t["img1"].shape[1:3]), ops.resize_size(self.resize_inputs, t["img1"].shape[1:3])
-                self.input_C1, self.input_C2 = (input[k].to(dev, non_blocking=True) if dst is None else
+                self.input_C1, self.input_C2 = (input[k].to(dev, non_blocking=True) if dst is None or aug else
                                                 ops.resize_joints(input[k].to(dev, non_blocking=True), src, dst)
                                                 for k in ("C1", "C2"))
+            if aug:
+                size = self.resize_inputs or None
+                return self._set_decoded(lambda: ops.decode_inputs_affine(*[t[k] for k in raw], out_size=size),
+                                         paths=(input["H1_path"], input["H2_path"]) if "H1_path" in input else None)
             return self.set_input_raw(*[t[k] for k in raw], paths=(input["H1_path"], input["H2_path"]) if "H1_path" in input else None)
         if "resident" in input:
             # a batch of data.HandFolderLoader(resident=True) whose images already sit in the device's store: ONE kernel
@@ -554,7 +561,11 @@ class MMHandModel(torch.nn.Module):
                 f"resident batch prepared for --resize_inputs {rb.out_size or 0}, the model runs {self.resize_inputs or 0}"
             if "C1" in input and "C2" in input:
                 self.input_C1, self.input_C2 = input["C1"], input["C2"]
-            return self._set_decoded(lambda: ops.decode_inputs_indexed(rb.store, rb.idx, rb.uv_table, out_size=rb.out_size),
+            if getattr(rb, "xf", None) is not None:     # --augment_geom: this epoch's matrices and joints, per sample
+                decode = lambda: ops.decode_inputs_indexed_affine(rb.store, rb.idx, rb.uv, rb.xf, out_size=rb.out_size)  # noqa: E731
+            else:
+                decode = lambda: ops.decode_inputs_indexed(rb.store, rb.idx, rb.uv_table, out_size=rb.out_size)          # noqa: E731
+            return self._set_decoded(decode,
                                      paths=(input["H1_path"], input["H2_path"]) if "H1_path" in input else None)
         keys = ("H1", "P1", "D1", "H2", "P2", "D2")
         if dev.type == "cuda" and any(not input[k].is_cuda for k in keys):

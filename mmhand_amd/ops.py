@@ -3296,6 +3296,59 @@ def decode_inputs_indexed(store, idx, uv_table, out_size=None, sigma=6.0, status
     return xh1, xh2, xp, xd
 
 
+# --------------------------------------------------------------------------- geometric augmentation (--augment_geom)
+def _chk_xf(xf, B, dev):
+    assert xf.dtype == torch.float64 and xf.device == dev and xf.is_contiguous() and tuple(xf.shape) == (B, 2, 6), \
+        "xf: contiguous float64 [B,2,6] on the images' device (data.affine_inverse, one row per sample and side)"
+
+
+def _decode_outputs(B, Ho, Wo, dev):
+    return (torch.empty((B, Ho, Wo, 4), dtype=torch.float32, device=dev), torch.empty((B, Ho, Wo, 4), dtype=torch.float32, device=dev),
+            torch.empty((B, Ho, Wo, 44), dtype=torch.float32, device=dev), torch.empty((B, Ho, Wo, 8), dtype=torch.float32, device=dev))
+
+
+def decode_inputs_affine(img1, img2, dep1, dep2, uv1, uv2, xf, out_size=None, sigma=6.0):
+    """decode_inputs sampling through one inverse affine map per image (mmh_decode_inputs_affine): xf float64 [B,2,6] takes an
+    output pixel to a source coordinate, side 0 for img1 / dep1, side 1 for img2 / dep2 (bilinear on pixel coordinates, edge
+    replicate = F.grid_sample(padding_mode="border", align_corners=True)).  uv1, uv2 are joints ALREADY on the output grid
+    (data.affine_joints: nothing is scaled here); out_size None = the sources' size.  The matrices are the caller's to keep
+    finite (data.affine_inverse refuses others); the kernel clamps whatever it is given."""
+    B, H, W_, _ = img1.shape
+    for t in (img1, img2, dep1, dep2):
+        assert t.dtype == torch.uint8 and t.is_cuda and t.is_contiguous() and tuple(t.shape) == (B, H, W_, 3)
+    dev = img1.device
+    for t in (uv1, uv2):
+        assert t.dtype == torch.float64 and t.device == dev and t.is_contiguous() and tuple(t.shape) == (B, 21, 2)
+    _chk_xf(xf, B, dev)
+    Ho, Wo = resize_size(out_size, (H, W_)) or (H, W_)
+    xh1, xh2, xp, xd = _decode_outputs(B, Ho, Wo, dev)
+    L.call("mmh_decode_inputs_affine", _ptr(img1), _ptr(img2), _ptr(dep1), _ptr(dep2), _ptr(uv1), _ptr(uv2), _ptr(xf),
+           B, H, W_, Ho, Wo, float(sigma), _ptr(xh1), _ptr(xh2), _ptr(xp), _ptr(xd), _stream())
+    return xh1, xh2, xp, xd
+
+
+def decode_inputs_indexed_affine(store, idx, uv, xf, out_size=None, sigma=6.0, status=None):
+    """decode_inputs_affine with the sources read out of a resident store (mmh_decode_inputs_indexed_affine): idx int32 [B,4]
+    as decode_inputs_indexed takes it, uv float64 [B,2,21,2] = the joints of each SAMPLE's two sides already on the output
+    grid (they change with the epoch's transform, so there is no per-slot table), xf float64 [B,2,6].  Bit for bit what
+    decode_inputs_affine makes of the same images; a sample with a slot outside [0, S) is zeros and ORs 1 into `status`."""
+    _chk_store(store)
+    S, Hs, Ws, _ = store.shape
+    dev = store.device
+    assert idx.dtype == torch.int32 and idx.device == dev and idx.is_contiguous() and idx.dim() == 2 and \
+        idx.shape[0] >= 1 and idx.shape[1] == 4, "idx: contiguous int32 [B,4] on the store's device"
+    B = idx.shape[0]
+    assert uv.dtype == torch.float64 and uv.device == dev and uv.is_contiguous() and tuple(uv.shape) == (B, 2, 21, 2), \
+        "uv: contiguous float64 [B,2,21,2] on the store's device"
+    _chk_xf(xf, B, dev)
+    _chk_status(status, dev)
+    Ho, Wo = resize_size(out_size, (Hs, Ws)) or (Hs, Ws)
+    xh1, xh2, xp, xd = _decode_outputs(B, Ho, Wo, dev)
+    L.call("mmh_decode_inputs_indexed_affine", _ptr(store), S, Hs, Ws, _ptr(idx), _ptr(uv), _ptr(xf), B, Ho, Wo,
+           float(sigma), _ptr(xh1), _ptr(xh2), _ptr(xp), _ptr(xd), _ptr(status), _stream())
+    return xh1, xh2, xp, xd
+
+
 # ----------------------------------------------------------------------------- pose distance (csrc/pose_knn.hip)
 def _chk_pose_features(F, valid, what):
     assert F.is_cuda and F.dtype == torch.float64 and F.is_contiguous() and F.dim() == 2 and F.shape[1] == 64 and \

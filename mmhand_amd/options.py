@@ -27,7 +27,10 @@ Differences, all deliberate:
   * --resident_dataset / --resident_gb G (additions; off): the file-fed loader keeps the decoded dataset in device memory
     after the first epoch (data.HandFolderLoader(resident=True));
   * --pairing random | curriculum | nearest, --match_pool self | train (additions; random = the reference's live loader):
-    the paper's pairing strategies on the reference's pose distance (data.HandFolderLoader, csrc/pose_knn.hip).
+    the paper's pairing strategies on the reference's pose distance (data.HandFolderLoader, csrc/pose_knn.hip);
+  * --augment_geom with --aug_rotate / --aug_scale / --aug_shift / --aug_flip / --aug_pair / --aug_seed (additions to `train`;
+    off): a random affine transform per image and epoch inside the device's decode pass (data.augment_draws,
+    ops.decode_inputs_affine).  The reference declares --no_flip / --use_flip and never reads them; they stay dead here.
 """
 import argparse
 import os
@@ -147,6 +150,19 @@ _TRAIN = [
     ("--percep_is_l1", dict(type=int, default=1)),
     ("--no_dropout_D", dict(action="store_true")),
     ("--DG_ratio", dict(type=int, default=1)),
+    ("--augment_geom", dict(action="store_true",
+                            help="with --dataroot: a random rotation, scale, shift (and flip) per image and epoch, sampled "
+                                 "inside the device's decode pass (mmh_decode_inputs_affine; bilinear, edge replicate); joints "
+                                 "transformed with the pixels, sigma unchanged")),
+    ("--aug_rotate", dict(type=float, default=15.0, help="with --augment_geom: degrees, theta ~ U(-r, r)")),
+    ("--aug_scale", dict(type=float, default=0.1, help="with --augment_geom: s ~ U(1 - a, 1 + a), 0 <= a < 1")),
+    ("--aug_shift", dict(type=float, default=0.05, help="with --augment_geom: shift ~ U(-f, f) of the image size, per axis")),
+    ("--aug_flip", dict(type=float, default=0.0,
+                        help="with --augment_geom: probability of a horizontal flip (0 by default: a mirrored hand is the other hand)")),
+    ("--aug_pair", dict(type=str, default="shared", choices=["shared", "independent"],
+                        help="with --augment_geom: shared - source and target of a pair take one draw (the pair keeps the "
+                             "relation it has in the data, background included); independent - each draws its own")),
+    ("--aug_seed", dict(type=int, default=0, help="with --augment_geom: seed of the draws (with the epoch number)")),
 ]
 _TEST = [
     ("--ntest", dict(type=int, default=float("inf"))),
@@ -176,6 +192,43 @@ def check_resize_inputs(opt):
     return n
 
 
+AUG_PAIRS = ("shared", "independent")
+
+
+def check_augment(opt):
+    """--augment_geom and its ranges, validated; absent attributes are the defaults.  Returns None when the flag is off, else
+    (rotate, scale, shift, flip, pair, seed)."""
+    if not getattr(opt, "augment_geom", False):
+        return None
+
+    def num(name, default):
+        v = getattr(opt, name, default)
+        v = default if v is None else v
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or v != v or v in (float("inf"), float("-inf")):
+            raise ValueError(f"--{name} {v!r}: a finite number expected")
+        return float(v)
+
+    rotate, scale, shift, flip = num("aug_rotate", 15.0), num("aug_scale", 0.1), num("aug_shift", 0.05), num("aug_flip", 0.0)
+    if not 0.0 <= rotate <= 180.0:
+        raise ValueError(f"--aug_rotate {rotate!r}: expected degrees in [0, 180]")
+    if not 0.0 <= scale < 1.0:
+        raise ValueError(f"--aug_scale {scale!r}: expected 0 <= a < 1 (s ~ U(1 - a, 1 + a) must stay positive)")
+    if not 0.0 <= shift <= 1.0:
+        raise ValueError(f"--aug_shift {shift!r}: expected a fraction of the image size in [0, 1]")
+    if not 0.0 <= flip <= 1.0:
+        raise ValueError(f"--aug_flip {flip!r}: expected a probability in [0, 1]")
+    pair = getattr(opt, "aug_pair", None) or "shared"
+    if pair not in AUG_PAIRS:
+        raise ValueError(f"--aug_pair {pair!r}: expected one of {' | '.join(AUG_PAIRS)}")
+    seed = getattr(opt, "aug_seed", 0)
+    seed = 0 if seed is None else seed
+    if isinstance(seed, bool) or not isinstance(seed, int) or seed < 0:
+        raise ValueError(f"--aug_seed {seed!r}: a non-negative integer expected")
+    if not getattr(opt, "dataroot", None):
+        raise ValueError("--augment_geom works with --dataroot only (the synthetic loader has no images to transform)")
+    return rotate, scale, shift, flip, pair, seed
+
+
 class BaseOptions:
     isTrain = None
     _extra = []
@@ -198,6 +251,7 @@ class BaseOptions:
         except ValueError as e:
             self.parser.error(str(e))
         check_resize_inputs(opt)        # a ValueError, as for a namespace built in code (MMHandModel checks those)
+        check_augment(opt)              # likewise (data.HandFolderLoader checks those)
         opt.isTrain = self.isTrain
         import torch
         if opt.distributed:
