@@ -1330,7 +1330,7 @@ __global__ void gate_bwd_kernel(const float* __restrict__ g_out, const void* __r
 // and 2 B per element of gate input are gone); backward, the gate's kernel - which recomputes s1 and produces the gradient
 // gs1 of the norm's output anyway - also leaves the norm backward's plane sums (sum gs1, sum gs1 * xhat) in the partial layout
 // and summation order of col_reduce_partial_v2<1>, so mmh_norm_bwd_reduce's pass over gs1 and y2 is gone as well.  Same
-// arithmetic, same order: bit-identical to the unfused sequence (tests/test_pointwise_gpu.py).
+// arithmetic, same order: bit-identical to the unfused sequence (tests/test_lp16_step_gpu.py).
 // Geometry as the other second-generation row kernels: block = (256 / C8 rows) x C8 lanes of 8 channels, grid (chunks, groups).
 template <bool SW>      // SW: s2 / s3 are 16-bit
 __global__ void __launch_bounds__(TPB) gate_norm_fwd_kernel(
@@ -1490,11 +1490,17 @@ __global__ void loss_partial_kernel(const float* __restrict__ a, const float* __
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 // softplus(-|x|) = log1p(exp(-|x|)): libm's log1pf made this pass COMPUTE-bound (~60 instructions per element:
-                // 99 us for the 134 MB of one discriminator map, 1.35 TB/s).  t = exp(-|x|) is in (0, 1]: the hardware log of
-                // 1 + t is exact to an ulp where t >= 2^-10, and below it two series terms are (error t^3 / 3 < 4e-10 relative)
+                // 99 us for the 134 MB of one discriminator map, 1.35 TB/s).  t = exp(-|x|) is in (0, 1].  Below 2^-10 two series
+                // terms do (t^2 / 3 < 3.2e-7 relative).  Above it the hardware log of u = fl(1 + t) is good to an ulp, but the SUM
+                // is not: rounding 1 + t drops up to 2^-24 of t, 6e-5 of the result at t = 2^-10 (|x| = 6.93) and above the tests'
+                // 2e-5 down to |x| = 5.8.  d = t - (u - 1) is that dropped part, exactly (u - 1 and the difference are both
+                // representable), and log(u + d) = log(u) + d / u - ..: adding d itself leaves d * t / u < 2^-24 t.
+                // This relies on IEEE evaluation order: the build must never enable fast-math or reassociation (the Makefile
+                // passes neither), or t - (u - 1) folds to 0.
                 const float x = xs[e];
                 const float t = __expf(-fabsf(x));
-                const float sp = t < 9.765625e-4f ? t * (1.f - 0.5f * t) : __logf(1.f + t);
+                const float u = 1.f + t;
+                const float sp = t < 9.765625e-4f ? t * (1.f - 0.5f * t) : __logf(u) + (t - (u - 1.f));
                 acc += fmaxf(x, 0.f) - x * target + sp;
             }
         } else if (MODE == 1) {
@@ -2348,16 +2354,21 @@ __global__ void prep_weights_bf16_flat_kernel(const float* __restrict__ w, int t
 
 inline bool is_dtype(int d) { return d == MMH_F32 || d == MMH_BF16 || d == MMH_FP16; }
 
-int check_cols(const char* who, int C) {
-    MMH_REQUIRE(C > 0 && C % 4 == 0 && C <= 1024, "%s: C must be a multiple of 4 in (0,1024], got %d",
-                who, C);
+// max_c: 1024 for everything that reduces over rows (column sums staged through LDS); the purely row-wise kernels (scale-shift-
+// activation, the PATBlock gate) handle up to 8 * TPB = 2048 channels - row_geom_ok()'s c8 <= TPB, one row per block iteration
+int check_cols(const char* who, int C, int max_c = 1024) {
+    MMH_REQUIRE(C > 0 && C % 4 == 0 && C <= max_c, "%s: C must be a multiple of 4 in (0,%d], got %d",
+                who, max_c, C);
     return 0;
 }
 
 
 // MaxPool2d(2, 2) on NHWC fp32 (the pooling layers of vgg19.features when --perceptual_layers reaches past index 3:
 // losses/L1_plus_perceptualLoss.py:22-27).  One lane per (output pixel, 4 channels).  Backward: the gradient goes to the
-// FIRST maximum of the window in scan order (0,0), (0,1), (1,0), (1,1) - what torch's max_pool2d does.
+// FIRST maximum of the window in scan order (0,0), (0,1), (1,0), (1,1) - what torch's max_pool2d does
+// (tests/test_pointwise_exact_gpu.py, on tied integer inputs).  NaN: fmaxf returns the other operand, so the forward DROPS a NaN
+// that torch's max_pool2d propagates (and the backward's comparisons never select one); VGG features are finite, and a
+// non-finite gradient is caught by mmh_grad_nonfinite, not here.
 __global__ void maxpool2_fwd_kernel(const float* __restrict__ x, float* __restrict__ y, int B, int H, int W, int C4) {
     const int Ho = H / 2, Wo = W / 2;
     const int64_t total = (int64_t)B * Ho * Wo * C4;
@@ -2522,7 +2533,7 @@ static int scale_shift_act_impl(const void* x, const void* scale, const void* sh
                                 void* out, int groups, int64_t rows, int C, int relu, float drop_p,
                                 uint64_t seed, const void* mask, void* keep_bits, int x_dtype, int out_dtype,
                                 void* twin, int twin_dtype, mmh_stream_t s) {
-    if (int rc = check_cols("mmh_scale_shift_act", C)) return rc;
+    if (int rc = check_cols("mmh_scale_shift_act", C, 8 * TPB)) return rc;
     MMH_REQUIRE(!twin || (mmh::g_pw_v2 && row_geom_ok(C) && (twin_dtype == MMH_BF16 || twin_dtype == MMH_FP16)),
                 "mmh_scale_shift_act_twin: the 16-bit twin needs C / 8 a power of two <= 256 and a 16-bit twin_dtype");
     MMH_REQUIRE(x && scale && shift && out && groups > 0 && rows > 0, "mmh_scale_shift_act: bad arguments");
@@ -2871,7 +2882,7 @@ int mmh_act_bwd_lp16_io(const void* g, int g_is16, const void* y, int y_is16, in
 int mmh_patblock_gate_fwd(const void* x1, const void* s1, const void* s2, const void* s3, void* out,
                           void* x2n, void* x3n, int64_t rows, int C, int cat_dtype, int s23_dtype,
                           mmh_stream_t s) {
-    if (int rc = check_cols("mmh_patblock_gate_fwd", C)) return rc;
+    if (int rc = check_cols("mmh_patblock_gate_fwd", C, 8 * TPB)) return rc;
     MMH_REQUIRE(is_dtype(cat_dtype) && is_dtype(s23_dtype),
                 "mmh_patblock_gate_fwd: cat_dtype / s23_dtype must be MMH_F32 | MMH_BF16 | MMH_FP16");
     MMH_REQUIRE(x1 && s1 && s2 && s3 && out && rows > 0 && ((x2n == nullptr) == (x3n == nullptr)),
@@ -2887,7 +2898,7 @@ int mmh_patblock_gate_bwd(const void* g_out, const void* g_x2n, const void* g_x3
                           const void* s2, const void* s3, void* g_x1, void* g_s1, void* g_s2,
                           void* g_s3, int64_t rows, int C, int gcat_dtype, int s23_dtype, int gs23_dtype,
                           mmh_stream_t s) {
-    if (int rc = check_cols("mmh_patblock_gate_bwd", C)) return rc;
+    if (int rc = check_cols("mmh_patblock_gate_bwd", C, 8 * TPB)) return rc;
     MMH_REQUIRE(is_dtype(gcat_dtype) && is_dtype(s23_dtype) && is_dtype(gs23_dtype),
                 "mmh_patblock_gate_bwd: bad gcat_dtype / s23_dtype / gs23_dtype");
     MMH_REQUIRE(s1 && s2 && s3 && g_x1 && g_s1 && g_s2 && g_s3 && rows > 0,
