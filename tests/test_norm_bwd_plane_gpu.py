@@ -4,7 +4,11 @@ against the two-pass entry points it replaces (mmh_norm_bwd_reduce + mmh_norm_bw
 
 The per-element arithmetic is the two-pass kernels' regrouped (three coefficients instead of four) and the plane sums are
 taken in a different fixed order, so the results agree to rounding, not bit for bit: sums within 2e-6 relative, a 16-bit dx
-within one unit in the last place on a few elements (relative L1 <= 1e-3 bf16 / 2e-4 fp16), an fp32 dx within 2e-6."""
+within one unit in the last place on a few elements (relative L1 <= 1e-3 bf16 / 2e-4 fp16), an fp32 dx within 2e-6.
+
+On dyadic inputs there is no rounding: tests/test_norm_exact_gpu.py::test_one_pass_norm_backward_exact holds the sums and
+every element of dx to float64 exactly, and to the two-pass result element for element, in each lpr_log2 geometry and on
+both sides of the `tail` path.  The tests here stay: realistic values and count = rows."""
 import ctypes as C
 
 import pytest

@@ -5,7 +5,10 @@ has none; 5000 x 256: 156 chunks of 33 rows, the last four have none) - the kern
 
 Sums of integers are exact whatever the partition: the column sums and s1 = sum dz of the norm backward (integer g, keep bits,
 drop_p 0.5 or 0 - a scale of 2 or 1) are held to float64 element by element (tests/_exact.py).  Everything else keeps the
-tolerances of tests/test_pointwise_gpu.py (imported, not copied).  Knobs go through E.option(), which restores what the key had."""
+tolerances of tests/test_pointwise_gpu.py (imported, not copied).  Knobs go through E.option(), which restores what the key had.
+
+tests/test_norm_exact_gpu.py holds s2 and every element of dx EXACTLY on dyadic inputs (tests/_norm_oracle.py) at the default
+partition; the tolerance tests here stay: they are the ones with realistic values, count = rows and every partition."""
 import itertools
 
 import pytest
@@ -13,6 +16,7 @@ import torch
 
 from oracle import ops_ref as R
 from tests import _exact as E
+from tests._norm_oracle import drop_bytes as _drop_bytes, keep_bytes as _keep_bytes      # the keep-mask layouts, shared with the exact tests
 from tests.test_pointwise_gpu import GRAD_TOL, TOL, _mk
 
 pytestmark = pytest.mark.gpu
@@ -67,21 +71,6 @@ def test_exact_colsum_of_a_strided_matrix(dev):
             out = torch.full((C,), 7.0, device=dev)
             lib.call("mmh_colsum", wd.data_ptr(), rows, C, cs, out.data_ptr(), ws.data_ptr(), nws, 0, lib.F32, _stream())
             E.assert_exact(out, want, f"strided colsum {combo}")
-
-
-def _keep_bytes(keep):
-    """bool [.., C] -> uint8 [.., C / 4]: bit e of a byte = lane e of its float4 (the layout mmh_scale_shift_act writes)"""
-    k = keep.reshape(*keep.shape[:-1], keep.shape[-1] // 4, 4).to(torch.uint8)
-    return k[..., 0] | (k[..., 1] << 1) | (k[..., 2] << 2) | (k[..., 3] << 3)
-
-
-def _drop_bytes(keep):
-    """bool [.., C] -> uint8 [.., C / 8]: one bit per element (the layout of mmh_dropout_bits)"""
-    k = keep.reshape(*keep.shape[:-1], keep.shape[-1] // 8, 8).to(torch.uint8)
-    out = torch.zeros(k.shape[:-1], dtype=torch.uint8)
-    for e in range(8):
-        out |= k[..., e] << e
-    return out
 
 
 def _bwd_reference(g, keep, dsc, x, mean, invstd, rows):
