@@ -81,6 +81,8 @@ int mmh_version(void);
  * Every key (mmh_option_key enumerates the same list):
  *   fp32 implicit GEMM   "conv_dbuf" "conv_cw" "conv_bn256" "conv_levels" (1 | 2) "conv_xcd" "conv_xcd1" "conv_tall"
  *                        "dgrad_s2_multi" "dgrad_s2_halo" "border_bn64" "stem_f32"
+ *   sparse fp32 stems    "stem_sparse" (1: the mmh_conv7_stem_sparse_*_supported queries may say yes, 0: they say no and
+ *                        every caller stays on the dense kernels - the forward is bit-identical either way)
  *   fp32 wgrad           "wgrad_slots" "wgrad_dbuf" "wgrad_bn256" "wgrad_xcd" "wgrad_s2_strip" "slab_reduce_par"
  *   fp32 Winograd        "wino_bn256" "wino_xcd" "wino_gemm_v2" "wino_gemm_occ" "wino_gemm_bn" "wino_gemm_levels"
  *                        "wino_bf16_bk" "wino_bf16_occ" "wino6_vec" "wino_wgrad_v2" "wino_wgrad_occ"
@@ -732,6 +734,33 @@ int mmh_conv7_stem_wgrad_supported(const mmh_conv_desc* d);
 size_t mmh_conv7_stem_wgrad_ws_bytes(const mmh_conv_desc* d);
 int mmh_conv7_stem_wgrad(const mmh_conv_desc* d, const void* x, const void* dy, void* dw,
                          void* ws, size_t ws_bytes, int accumulate, mmh_stream_t s);
+
+/* ---- compacted-channel fp32 7x7 stems for inputs that are mostly pose heat maps (stem_sparse.hip) -----
+ * The Generator's pose stem and D_PB (models/Generator.py:158-164, models/Discriminator.py:60-64) read 21 / 42 truncated
+ * Gaussians (about 1.6 % of a 256 x 256 map is non-zero); these kernels contract over the channels that are active in a tile.
+ *
+ * mmh_stem_activity: x fp32 NHWC [B,H,W,C] dense (4 <= C <= 48, C % 4 == 0, H % 8 == 0, W % 16 == 0, 16-byte aligned) ->
+ *   mask uint64 [B][H/8][W/16] (mmh_stem_activity_bytes; 0 for an unsupported shape): bit c is set iff channel c has an
+ *   element != 0 (-0.0 counts as zero, NaN as non-zero) inside the block's 8 x 16 pixels plus the 3-pixel halo, read through
+ *   the ReflectionPad2d(3) index map.  Exact; one pass; every block writes its own word.
+ * mmh_conv7_stem_sparse_fprop: what mmh_conv2d_fprop_stats writes for the same stem (y and the whole stats buffer, stats may
+ *   be NULL), bit for bit, for finite weights (an omitted term is fmaf(0, w, acc); with a non-finite w the dense kernel gives
+ *   NaN where this one gives a number).  `mask` must be mmh_stem_activity of this x.  Not under "conv_levels" 2.
+ * mmh_conv7_stem_sparse_wgrad (W % 64 == 0): dw [7][7][Cin][64] fp32 (+)= the stem's weight gradient; a workgroup per (input
+ *   channel, split) walks mmh_conv7_stem_wgrad's 2 x 64 pixel tiles of that split in its order and multiplies only those
+ *   whose mask words have the channel; slabs [splits][7][7][Cin][64] in ws (16-byte aligned) summed as that kernel's are.
+ *   Where mmh_conv7_stem_wgrad_supported(d), dw is that kernel's bit for bit (finite dy); elsewhere (24 lanes) it is the
+ *   same sum in another order than mmh_conv2d_wgrad's - callers that need the parent's bits keep the dense route there.
+ * Results never depend on the sparsity; a fully dense input is only slower.  "stem_sparse" 0 turns both _supported off.  */
+size_t mmh_stem_activity_bytes(int B, int H, int W);
+int mmh_stem_activity(const void* x, int B, int H, int W, int C, void* mask, mmh_stream_t s);
+int mmh_conv7_stem_sparse_fprop_supported(const mmh_conv_desc* d);
+int mmh_conv7_stem_sparse_fprop(const mmh_conv_desc* d, const void* x, const void* mask, const void* w, const void* bias,
+                                void* y, void* stats, mmh_stream_t s);
+int mmh_conv7_stem_sparse_wgrad_supported(const mmh_conv_desc* d);
+size_t mmh_conv7_stem_sparse_wgrad_ws_bytes(const mmh_conv_desc* d);
+int mmh_conv7_stem_sparse_wgrad(const mmh_conv_desc* d, const void* x, const void* mask, const void* dy, void* dw, void* ws,
+                                size_t ws_bytes, int accumulate, mmh_stream_t s);
 
 /* ---- Adam (torch.optim.Adam, MMHandModel.py:90-98) over a flat buffer ------
  * step is the 1-based step count; no weight decay, no amsgrad.

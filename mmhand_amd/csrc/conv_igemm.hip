@@ -3226,6 +3226,7 @@ const OptionEntry* option_table(int* count) {
         {"wino_bf16_bk", &g_wino_bf16_bk},
         {"wino_wgrad_bn256", &g_wino_wgrad_bn256},
         {"wino_wgrad_slots", &g_wino_wgrad_slots},
+        {"stem_sparse", &mmh::g_stem_sparse},
     };
     *count = (int)(sizeof(table) / sizeof(table[0]));
     return table;

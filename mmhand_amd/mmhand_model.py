@@ -354,6 +354,7 @@ class MMHandModel(torch.nn.Module):
             self.netD_PP = Discriminator(opt.H_input_nc + opt.H_input_nc, opt.ndf, norm,
                                          not opt.no_dropout_D, opt.n_layers_D,
                                          n_downsampling=opt.D_n_downsampling)
+            self.netD_PB.stem_conv().pose_input = True     # cat(image, P2): 21 of its 24 lanes are pose maps
             self.netD_PB.to(self.device).init_weights(opt.init_type, seed + 1)
             self.netD_PP.to(self.device).init_weights(opt.init_type, seed + 2)
             nets += [self.netD_PB, self.netD_PP]

@@ -32,6 +32,9 @@ class ConvParam(nn.Module):
         a, b = (pad4(cout), pad4(cin)) if transposed else (pad4(cin), pad4(cout))
         self.weight = nn.Parameter(torch.zeros(k, k, a, b))
         self.bias = nn.Parameter(torch.zeros(pad4(cout))) if bias else None
+        # the 7x7 stems that read pose heat maps (the Generator's pose stem, D_PB): _Net.conv asks for the input's activity
+        # mask, and the fp32 stem kernels then skip the channels that are all zero in a tile (ops.stem_mask_request)
+        self.pose_input = False
 
     # logical <-> physical --------------------------------------------------
     def logical_weight(self):
@@ -315,6 +318,8 @@ class _Net(nn.Module):
         # ... and the conv's epilogue leaves partial statistics of its output for that norm (ops.FUSE_NORM_STATS); a
         # bias-free conv in front of a BatchNorm gets them too (its statistics are merged over the whole batch)
         nb = bool(to_norm and self.training and (self.norm == "instance" or cp.bias is None))
+        if cp.pose_input and nb and x16 is None and not self.bf16 and cp.k == 7 and stride == 1 and pad == 3 and reflect:
+            ops.stem_mask_request(x, cp.weight.shape[3])    # training, statistics epilogue: the route the sparse fprop and wgrad stand in for
         if x16 is not None:
             res_tok = None      # tokens belong to fp32 block inputs (ops.ResidualToken)
         if y_lp:
@@ -535,6 +540,7 @@ class Generator(_Net):
         for s, nc in zip((1, 2, 3), input_nc):
             d = m.put(f"stream{s}_down", Bag())
             self._conv(d, 1, nc, ngf, 7)
+            d[1].pose_input = s == 2        # cat(P1, P2): truncated Gaussians, mostly zeros (ops.stem_mask_request)
             self._normp(d, 2, ngf)
             for i in range(n_downsampling):
                 c = ngf * 2 ** i
@@ -717,6 +723,10 @@ class Discriminator(_Net):
             self._normp(cb, 2, dim)
             self._conv(cb, i2, dim, dim, 3)
             self._normp(cb, i2 + 1, dim)
+
+    def stem_conv(self):
+        """the 7x7 stem's parameters (ReflectionPad2d(3) + Conv2d(input_nc, ngf, 7): models/Discriminator.py:60-64)"""
+        return self.model[1]
 
     def forward_nhwc(self, x, dx_channels=0):
         """dx_channels > 0: the caller needs the gradient of only the first dx_channels input

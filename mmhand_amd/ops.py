@@ -514,6 +514,65 @@ def _take_stats(x, peek=False):
     return pend
 
 
+# Activity masks of the fp32 7x7 stems whose input is mostly pose heat maps (stem_sparse.hip): one uint64 per 8 x 16 pixel
+# block, bit c = "channel c is not all zero in the block and its halo".  A caller that knows its tensor is such an input (the
+# Generator's pose stem, D_PB: networks.py) asks for the mask with stem_mask_request; the stem's fprop and wgrad then find it
+# under the tensor's address, as the norm finds _pending_stats.  An entry is valid for the tensor object it was made from, at
+# the version it was made from (an in-place write - a new batch copied into a captured iteration's static buffer - makes a
+# new mask), and only on the side of a graph capture it was made on: a mask computed eagerly is never baked into a captured
+# iteration (the replay would read it for every later batch), the capture launches its own mask pass and replays it.
+_stem_masks = {}
+
+
+def _stem_mask_for(x):
+    """the mask requested for this very tensor (address, shape, version, same side of a graph capture), else None"""
+    ent = _stem_masks.get(x.data_ptr())
+    if ent is None:
+        return None
+    if (ent[1] != tuple(x.shape) or ent[2] != x._version or ent[3]() is None
+            or ent[4] != torch.cuda.is_current_stream_capturing()):
+        return None
+    return ent[0]
+
+
+def stem_mask_forget(t):
+    """t (or a leading slice of it) is about to be overwritten by a kernel that takes a raw pointer - mmh_pack_nhwc* into the
+    static buffers of a captured iteration, into one half of a two-batch buffer: torch's version counter does not see that
+    write, so a mask cached for the old contents must go (an eager forward between two replays would otherwise skip what
+    the old batch did not have)"""
+    _stem_masks.pop(t.data_ptr(), None)
+
+
+def stem_mask_request(x, cout=64):
+    """x: fp32 NHWC [B,H,W,C], contiguous, the input of a 7x7 / stride 1 / ReflectionPad2d(3) stem with cout output channels
+    -> its activity mask (int64 [B * H/8 * W/16]), computed once per (tensor, version); None - and no mask pass - where
+    neither sparse kernel takes that conv (shape, width, "stem_sparse" 0): the stem then runs the dense kernels"""
+    if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.is_contiguous()):
+        return None
+    B, H, W_, Cc = x.shape
+    nbytes = L.load().mmh_stem_activity_bytes(B, H, W_)
+    if nbytes == 0 or Cc % 4 or not 4 <= Cc <= 48 or x.numel() >= 2 ** 31 or x.data_ptr() % 16:
+        return None
+    d = conv_desc(B, H, W_, Cc, cout, 7, 1, 3, True)
+    # both queries say no under "stem_sparse" 0; under "conv_levels" 2 only the wgrad takes the mask
+    if not (L.load().mmh_conv7_stem_sparse_fprop_supported(C.byref(d))
+            or (USE_STEM_WGRAD and L.load().mmh_conv7_stem_wgrad_supported(C.byref(d))
+                and L.load().mmh_conv7_stem_sparse_wgrad_supported(C.byref(d)))):
+        return None
+    mask = _stem_mask_for(x)
+    if mask is not None:
+        return mask
+    if len(_stem_masks) >= 8:
+        # only entries whose tensor is gone: a live one is still owed to its stem's wgrad (dropping it would send that
+        # wgrad to the dense kernel, five times as long, depending on what else happened to be cached)
+        for k in [k for k, e in _stem_masks.items() if e[3]() is None]:
+            del _stem_masks[k]
+    mask = torch.empty((nbytes // 8,), dtype=torch.int64, device=x.device)
+    L.call("mmh_stem_activity", _ptr(x), B, H, W_, Cc, _ptr(mask), _stream())
+    _stem_masks[x.data_ptr()] = (mask, tuple(x.shape), x._version, weakref.ref(x), torch.cuda.is_current_stream_capturing())
+    return mask
+
+
 def _wino_conv(x, U, bias, Cout, reflect, act, tile, time_it=False, keep_V=False, bf16=False, want_stats=False,
                fold=False, pro=None, levels=0, levels16=0):
     """input transform -> P batched GEMMs (one launch) -> output transform (+bias, activation).
@@ -739,7 +798,14 @@ def raw_conv_fprop(x, w, bias, stride, pad, reflect, act=L.ACT_NONE, bf16=False,
         chunks = L.load().mmh_conv2d_fprop_stats_chunks(C.byref(d))
         if chunks > 0:
             stats = _empty((B, chunks // B, 3, Cout), x)
-            L.call("mmh_conv2d_fprop_stats", C.byref(d), _ptr(x), _ptr(w), _ptr(bias), _ptr(y), _ptr(stats), _stream())
+            mask = _stem_mask_for(x)
+            if mask is not None and L.load().mmh_conv7_stem_sparse_fprop_supported(C.byref(d)):
+                # a pose-map stem whose caller asked for an activity mask: the same y and stats, bit for bit, from the
+                # channels that are active in each tile (stem_sparse.hip)
+                L.call("mmh_conv7_stem_sparse_fprop", C.byref(d), _ptr(x), _ptr(mask), _ptr(w), _ptr(bias), _ptr(y),
+                       _ptr(stats), _stream())
+            else:
+                L.call("mmh_conv2d_fprop_stats", C.byref(d), _ptr(x), _ptr(w), _ptr(bias), _ptr(y), _ptr(stats), _stream())
             _park_stats(y, stats)
             return y
     if fprop_timer is not None and fprop_timer.want(d):
@@ -988,6 +1054,18 @@ def raw_conv_wgrad(x, dy, k, stride, pad, reflect, bf16=False, out=None):
         L.call("mmh_conv7_thin_wgrad", C.byref(d), _ptr(x), _ptr(dy), _ptr(dw), _ptr(ws), ws.numel() * 4,
                int(out is not None), _stream())
         _count_desc("valu", d)
+        return dw
+    mask = None if (bf16 or not x.is_contiguous()) else _stem_mask_for(x)
+    if (mask is not None and dy.is_contiguous() and USE_STEM_WGRAD and L.load().mmh_conv7_stem_wgrad_supported(C.byref(d))
+            and L.load().mmh_conv7_stem_sparse_wgrad_supported(C.byref(d))):
+        # a pose-map stem whose caller asked for an activity mask: per input channel, only the tiles that see it.  Taken only
+        # where the dense route is mmh_conv7_stem_wgrad (44 lanes: the Generator's pose stem), whose tiles, splits and pixel
+        # order the sparse kernel keeps - the same dw bit for bit.  D_PB (24 lanes) stays on the generic wgrad: another order
+        ws = _ws(L.load().mmh_conv7_stem_sparse_wgrad_ws_bytes(C.byref(d)), x)
+        dw = out if out is not None else _empty((k, k, Cin, Cout), x)
+        L.call("mmh_conv7_stem_sparse_wgrad", C.byref(d), _ptr(x), _ptr(mask), _ptr(dy), _ptr(dw), _ptr(ws), ws.numel() * 4,
+               int(out is not None), _stream())
+        _count_desc("mfma", d)
         return dw
     if USE_STEM_WGRAD and not bf16 and L.load().mmh_conv7_stem_wgrad_supported(C.byref(d)):
         # fp32 7x7 stems (Cin <= 44 -> 64): the input band of a filter row staged in LDS once instead of a
@@ -3061,6 +3139,7 @@ def raw_pack(srcs, B, H, W_, Cd, device, out=None, twin=0, twin_out=None, only16
         out = torch.empty((B, H, W_, Cd), dtype=torch.float32, device=device)
     else:
         assert tuple(out.shape) == (B, H, W_, Cd) and out.is_contiguous() and out.dtype == torch.float32
+        stem_mask_forget(out)       # the kernel writes through a raw pointer: out._version does not move
     if not tiled:
         L.call("mmh_pack_nhwc", arr, len(srcs), _ptr(out), B, H, W_, Cd, 0, _stream())
         return out
