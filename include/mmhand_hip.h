@@ -83,6 +83,7 @@ int mmh_version(void);
  *                        "dgrad_s2_multi" "dgrad_s2_halo" "border_bn64" "stem_f32"
  *   sparse fp32 stems    "stem_sparse" (1: the mmh_conv7_stem_sparse_*_supported queries may say yes, 0: they say no and
  *                        every caller stays on the dense kernels - the forward is bit-identical either way)
+ *                        "stem_sparse_flat" (0: only mmh_conv7_stem_sparse_wgrad_flat_supported says no)
  *   fp32 wgrad           "wgrad_slots" "wgrad_dbuf" "wgrad_bn256" "wgrad_xcd" "wgrad_s2_strip" "slab_reduce_par"
  *   fp32 Winograd        "wino_bn256" "wino_xcd" "wino_gemm_v2" "wino_gemm_occ" "wino_gemm_bn" "wino_gemm_levels"
  *                        "wino_bf16_bk" "wino_bf16_occ" "wino6_vec" "wino_wgrad_v2" "wino_wgrad_occ"
@@ -761,6 +762,17 @@ int mmh_conv7_stem_sparse_wgrad_supported(const mmh_conv_desc* d);
 size_t mmh_conv7_stem_sparse_wgrad_ws_bytes(const mmh_conv_desc* d);
 int mmh_conv7_stem_sparse_wgrad(const mmh_conv_desc* d, const void* x, const void* mask, const void* dy, void* dw, void* ws,
                                 size_t ws_bytes, int accumulate, mmh_stream_t s);
+/* mmh_conv7_stem_sparse_wgrad_flat (W % 16 == 0, B H W < 2^25, x 16-byte aligned, x_cs % 4 == 0): the same gradient in the
+ *   order of mmh_conv2d_wgrad's generic kernel, the dense route of the stems mmh_conv7_stem_wgrad does not take (D_PB, 24
+ *   lanes): its splits and pixels per split (one shared rule: option "wgrad_slots" moves both), its 32-pixel k-steps and
+ *   k-slot pairs, its slab sum.  A workgroup per (group of four adjacent lanes, split) multiplies a step only for the
+ *   lanes whose bit one of the step's two mask words has; always-active lanes share their group's pass over dy.  dw is
+ *   mmh_conv2d_wgrad's bit for bit (finite dy, up to the sign of an exact zero); ws_bytes equals
+ *   mmh_conv2d_wgrad_ws_bytes(d).  _supported is 0 under "stem_sparse" 0 or "stem_sparse_flat" 0 (default 1).          */
+int mmh_conv7_stem_sparse_wgrad_flat_supported(const mmh_conv_desc* d);
+size_t mmh_conv7_stem_sparse_wgrad_flat_ws_bytes(const mmh_conv_desc* d);
+int mmh_conv7_stem_sparse_wgrad_flat(const mmh_conv_desc* d, const void* x, const void* mask, const void* dy, void* dw, void* ws,
+                                     size_t ws_bytes, int accumulate, mmh_stream_t s);
 
 /* ---- Adam (torch.optim.Adam, MMHandModel.py:90-98) over a flat buffer ------
  * step is the 1-based step count; no weight decay, no amsgrad.

@@ -64,6 +64,11 @@ int launch_stem_f32(const mmh_conv_desc* d, const void* x, const void* w, const 
 extern int g_stem_f32, g_stem_f32_dbg, g_stem_f32_levels;
 // 1: the compacted-channel stem kernels answer "supported" (stem_sparse.hip), 0: every caller stays on the dense kernels
 extern int g_stem_sparse;
+// 1: D_PB's stem wgrad (the generic kernel's route) on stem_sparse_wgrad_flat_kernel where a mask exists, 0: stays dense
+extern int g_stem_sparse_flat;
+// the generic fp32 wgrad's split-K rule (conv_igemm.hip, do_wgrad): split s owns the flat dy-domain pixels
+// [s * pix_per_split, min(P, (s + 1) * pix_per_split)), pix_per_split a multiple of its 32-pixel k-step
+void wgrad_flat_split(int Mrows, int N, int P, int& splits, int& pix_per_split);
 // fp32 Winograd-domain wgrad GEMMs as a three-stage LDS-DMA ring (wino_wgrad_dma.hip)
 bool wino_wgrad_dma_ok(int64_t tiles, int Cin, int Cout, int nbatch);
 size_t wino_wgrad_dma_ws_bytes(int64_t tiles, int Cin, int Cout, int nbatch);

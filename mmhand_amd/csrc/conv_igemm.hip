@@ -3088,6 +3088,9 @@ int wgrad_splits(int Mrows, int N, int P) {
     return best;
 }
 
+// pixels of the flat dy domain per split: whole k-steps
+int wgrad_pix_per_split(int P, int splits, int step) { return (int)(mmh::cdiv(mmh::cdiv(P, splits), step) * step); }
+
 int g_wgrad_dbuf = 0;   // tuning knob (mmh_set_option "wgrad_dbuf")
 
 template <int BN, int WM, int WN, bool DBUF>
@@ -3160,7 +3163,7 @@ int do_wgrad(const mmh_conv_desc* d, const void* x, const void* dy, void* dw, vo
     p.slab = static_cast<float*>(ws);
     const bool bf16 = is16(d->dtype);
     p.h16 = d->dtype == MMH_FP16;
-    p.pix_per_split = (int)(mmh::cdiv(mmh::cdiv(p.P, splits), bf16 ? BKP : BK) * (bf16 ? BKP : BK));
+    p.pix_per_split = wgrad_pix_per_split(p.P, splits, bf16 ? BKP : BK);
     p.dbg = g_conv_dbg;
     p.nsplit = splits;
     int rc;
@@ -3227,6 +3230,7 @@ const OptionEntry* option_table(int* count) {
         {"wino_wgrad_bn256", &g_wino_wgrad_bn256},
         {"wino_wgrad_slots", &g_wino_wgrad_slots},
         {"stem_sparse", &mmh::g_stem_sparse},
+        {"stem_sparse_flat", &mmh::g_stem_sparse_flat},
     };
     *count = (int)(sizeof(table) / sizeof(table[0]));
     return table;
@@ -3240,6 +3244,13 @@ const OptionEntry* find_option(const char* key) {
 }
 
 }  // namespace
+
+namespace mmh {
+void wgrad_flat_split(int Mrows, int N, int P, int& splits, int& pix_per_split) {
+    splits = wgrad_splits(Mrows, N, P);
+    pix_per_split = wgrad_pix_per_split(P, splits, BK);
+}
+}  // namespace mmh
 
 extern "C" {
 

@@ -15,13 +15,17 @@
 //                          runs a [49 taps -> 64] x [64] x [128 pixels] MFMA GEMM for every 2 x 64 pixel tile of the split
 //                          in which the channel is active, in the dense kernel's order: dw is conv_stem.hip's bit for bit.
 //                          Slabs [splits][7][7][C][64], summed by slab_reduce.hip exactly as the dense kernel's are.
+//   stem_sparse_wgrad_flat the same for the stems whose dense route is the generic wgrad of conv_igemm.hip (D_PB, 24 lanes): a
+//                          workgroup owns four adjacent channels and one of THAT kernel's splits of the flat pixel range and
+//                          multiplies a 32-pixel k-step only for the channels that are active in it: dw is conv_igemm.hip's
+//                          bit for bit.
 //
 // Plain global loads and LDS reads / writes only; no LDS-DMA, no cross-workgroup waits, no atomics; every loop is bounded by
 // a count read once.  The results never depend on the sparsity: a tile with every channel active runs the same loops.
 #include <algorithm>
 #include "stem_f32_epilogue.h"
 
-namespace mmh { int g_stem_sparse = 1; }
+namespace mmh { int g_stem_sparse = 1, g_stem_sparse_flat = 1; }
 
 namespace {
 using namespace mmh::dev;
@@ -351,6 +355,167 @@ void wgrad_splits(const mmh_conv_desc* d, int& tiles, int& tiles_per_split, int&
     tiles_per_split = (tiles + splits - 1) / splits;
 }
 
+// ---------------------------------------------------------------------------------------------------- wgrad, flat order
+// The generic wgrad (conv_igemm.hip, conv_wgrad_kernel + slab_reduce) is the dense route of the stems conv_stem.hip does
+// not take (D_PB: 24 lanes).  Per element of dw it sums ONE fmaf chain per split over the split's flat range of dy-domain
+// pixels (image, row, column ascending) in k-steps of 32 pixels, pixel 2 i of a step in k slot 0 of MFMA i and 2 i + 1 in
+// slot 1.  This kernel keeps the splits (mmh::wgrad_flat_split), the steps, the pairs and the slab sum, and leaves out the
+// steps in which a lane is all zero: dw is the generic kernel's bit for bit (up to the sign of an exact zero, finite dy).
+//
+// A workgroup owns a group of four adjacent lanes (one float4 of x per pixel) and a split.  W % 16 == 0 and 32-aligned steps
+// put each 16-pixel half of a step inside one 8 x 16 mask block - the second half on the next row where the step crosses a
+// row end - whose word covers the halo of every tap; a step is multiplied for the lanes whose bit either half has.
+// Lanes that are active everywhere (D_PB's three image lanes, wherever they sit) so share one pass over dy with their
+// group instead of taking one each, and a group of four sparse lanes reads dy only where one of them is active.
+constexpr int FS = 32;                          // pixels per step: the generic kernel's k-step
+constexpr int FHP = 7 * HC;                     // halo of a 16-pixel half: 7 rows x 22 columns
+constexpr int FNH = 2 * FHP;                    // halo pixels of a step
+constexpr int FCH = 256;                        // steps listed at a time, one per thread
+
+struct FlatWgradKP {
+    const float* x;         // [B][H][W][x_cs]
+    const unsigned long long* mask;     // [B][H/8][W/16]
+    const float* dy;        // [B][H][W][y_cs]
+    float* slab;            // [splits][49][Cin][64]
+    int H, W, Cin, x_cs, y_cs, BX, BY, P, pix_per_split;
+};
+
+// one step's operands into registers: its dy [32][64] (2 float4 per thread) and the lane group's halo (308 float4)
+__device__ __forceinline__ void flat_fetch(const FlatWgradKP& p, int step, int g, int tid, float4 (&dreg)[2], float4 (&hreg)[2]) {
+    const int pix0 = step * FS, HW = p.H * p.W;
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+        const int e = u * 256 + tid;            // float4 e of the step's [32][64]
+        dreg[u] = *reinterpret_cast<const float4*>(p.dy + (size_t)(pix0 + (e >> 4)) * (size_t)p.y_cs + 4 * (e & 15));
+    }
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+        const int e = min(u * 256 + tid, FNH - 1);          // the last threads repeat the last pixel and do not store it
+        const int half = e / FHP, r = e - half * FHP;
+        const int hr = r / HC, hc = r - hr * HC;
+        const int pix = pix0 + 16 * half;
+        const int b = pix / HW, rem = pix - b * HW;
+        const int row = rem / p.W, col = rem - row * p.W;
+        const int ih = reflect_idx(row - 3 + hr, p.H), iw = reflect_idx(col - 3 + hc, p.W);
+        hreg[u] = *reinterpret_cast<const float4*>(p.x + ((size_t)(b * p.H + ih) * p.W + iw) * (size_t)p.x_cs + 4 * g);
+    }
+}
+
+// workgroup (lane group g, split): 4 waves = (tap half mh, output-channel half nh), one 32x32 accumulator per lane of the
+// group: rows = taps 32 mh + ., columns = output channels 32 nh + .; per active step and active lane 16 MFMA 32x32x2.
+__global__ void __launch_bounds__(256) stem_sparse_wgrad_flat_kernel(const FlatWgradKP p) {
+    __shared__ __attribute__((aligned(16))) float dys[FS * 64];
+    __shared__ float planes[4 * FNH];           // [lane of the group][half][7][22]
+    __shared__ int list[FCH];                   // active steps of the chunk, ascending: step | lanes << 24 (step < 2^20)
+    __shared__ int wave_cnt[4];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int m = lane & 31, kg = lane >> 5;
+    const int mh = wave & 1, nh = wave >> 1;
+    // splits along x: the workgroups of one group - of the always-active lanes' above all - are consecutive in dispatch order
+    // and so spread evenly over the XCDs and CUs (group along x would put them on every other XCD: 24 lanes = 6 groups).
+    // Groups in the order first, last, second, ...: image lanes in front of the pose maps or behind them both start at once
+    // (scheduling only: every group runs the same code; in plain order image lanes at 21-23 come last and stack on the CUs
+    // that free up first: 2969 us against 1625 at B = 64, 256 x 256)
+    const int gy = blockIdx.y, split = blockIdx.x;
+    const int g = (gy & 1) ? (int)gridDim.y - 1 - (gy >> 1) : (gy >> 1);
+    const int HW = p.H * p.W;
+    const int pbeg = split * p.pix_per_split;
+    const int pend = min(p.P, pbeg + p.pix_per_split);
+    const int s0 = pbeg / FS;
+    const int ns = pend > pbeg ? (pend - pbeg) / FS : 0;        // P % 32 == 0: whole steps only; a split past P is empty
+
+    f32x16 acc[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc[q][i] = 0.f;
+    // this lane's tap (rows past 48 repeat tap 48 and are not stored) as a halo offset
+    const int tap = min(32 * mh + m, 48);
+    const int a_lane = (tap / 7) * HC + (tap % 7);
+
+    float4 dreg[2], hreg[2];
+#pragma unroll
+    for (int u = 0; u < 2; ++u) dreg[u] = hreg[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int c0 = 0; c0 < ns; c0 += FCH) {
+        // the chunk's steps in which a lane of the group is active
+        int lanes = 0;
+        if (c0 + tid < ns) {
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const int pix = (s0 + c0 + tid) * FS + 16 * h;
+                const int b = pix / HW, rem = pix - b * HW;
+                const int row = rem / p.W, col = rem - row * p.W;
+                lanes |= (int)((p.mask[((size_t)b * p.BY + row / BR) * p.BX + col / BC] >> (4 * g)) & 15ull);
+            }
+        }
+        const bool on = lanes != 0;
+        const unsigned long long bal = __ballot(on);
+        if (lane == 0) wave_cnt[wave] = __popcll(bal);
+        __syncthreads();
+        int rank = __popcll(bal & ((1ull << lane) - 1ull));
+        for (int v = 0; v < wave; ++v) rank += wave_cnt[v];
+        if (on) list[rank] = (s0 + c0 + tid) | (lanes << 24);
+        const int nlist = wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
+        __syncthreads();
+
+        if (nlist > 0) flat_fetch(p, list[0] & 0xffffff, g, tid, dreg, hreg);
+        for (int a = 0; a < nlist; ++a) {
+            const int act = __builtin_amdgcn_readfirstlane(list[a]) >> 24;
+#pragma unroll
+            for (int u = 0; u < 2; ++u) *reinterpret_cast<float4*>(dys + (u * 256 + tid) * 4) = dreg[u];
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+                const int e = u * 256 + tid;
+                if (e < FNH) {
+                    planes[e] = hreg[u].x; planes[FNH + e] = hreg[u].y;
+                    planes[2 * FNH + e] = hreg[u].z; planes[3 * FNH + e] = hreg[u].w;
+                }
+            }
+            __syncthreads();
+            if (a + 1 < nlist) flat_fetch(p, list[a + 1] & 0xffffff, g, tid, dreg, hreg);
+            // MFMA i: pixel 2 i in k slot 0, 2 i + 1 in slot 1 - the generic kernel's pairs
+            float bw[FS / 2];
+#pragma unroll
+            for (int i = 0; i < FS / 2; ++i) bw[i] = dys[(2 * i + kg) * 64 + 32 * nh + m];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                if ((act >> q) & 1) {
+                    float av[FS / 2];           // all 16 reads first, then the MFMAs back to back
+#pragma unroll
+                    for (int i = 0; i < FS / 2; ++i) {
+                        const int px = 2 * i + kg;
+                        av[i] = planes[q * FNH + (px >> 4) * FHP + a_lane + (px & 15)];
+                    }
+                    asm volatile("" : "+v"(av[0]), "+v"(av[1]), "+v"(av[2]), "+v"(av[3]), "+v"(av[4]), "+v"(av[5]), "+v"(av[6]),
+                                 "+v"(av[7]), "+v"(av[8]), "+v"(av[9]), "+v"(av[10]), "+v"(av[11]), "+v"(av[12]), "+v"(av[13]),
+                                 "+v"(av[14]), "+v"(av[15]));     // keeps the scheduler from sinking each read to its MFMA
+#pragma unroll
+                    for (int i = 0; i < FS / 2; ++i) acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[i], bw[i], acc[q], 0, 0, 0);
+                }
+            }
+            __syncthreads();
+        }
+    }
+    // every row of the group in this split's slab, also where nothing fired (the workspace is not zeroed).
+    // C/D layout: column = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
+    float* out = p.slab + (size_t)split * 49 * p.Cin * 64 + (size_t)(4 * g) * 64 + 32 * nh + m;
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int t = 32 * mh + (r & 3) + 8 * (r >> 2) + 4 * kg;
+            if (t < 49) out[((size_t)t * p.Cin + q) * 64] = acc[q][r];
+        }
+}
+
+bool wgrad_flat_ok(const mmh_conv_desc* d) {
+    return d && d->kh == 7 && d->kw == 7 && d->stride == 1 && d->pad == 3 && d->pad_mode == MMH_PAD_REFLECT &&
+           d->dtype == MMH_F32 && d->Cout == 64 && d->y_cs >= 64 && d->y_cs % 4 == 0 && d->Cin >= 4 && d->Cin <= CMAX &&
+           d->Cin % 4 == 0 && d->x_cs >= d->Cin && d->x_cs % 4 == 0 && d->H >= 8 && d->W >= 16 && d->H % BR == 0 &&
+           d->W % BC == 0 && d->Ho == d->H && d->Wo == d->W && d->B >= 1 &&
+           (size_t)d->B * d->H * d->W < (1ull << 31) / 64;
+}
+
 bool mask_args_ok(int B, int H, int W) {
     return B >= 1 && H >= 4 && W >= 4 && H % BR == 0 && W % BC == 0;
 }
@@ -447,6 +612,42 @@ int mmh_conv7_stem_sparse_wgrad(const mmh_conv_desc* d, const void* x, const voi
     hipStream_t st = mmh::as_stream(s);
     hipLaunchKernelGGL(stem_sparse_wgrad_kernel, dim3(d->Cin, splits), dim3(WNT), lds, st, p);
     if (int rc = mmh::check_launch("stem_sparse_wgrad_kernel")) return rc;
+    const int n4 = 49 * d->Cin * 64 / 4;
+    return mmh::launch_slab_reduce(p.slab, static_cast<float*>(dw), n4, splits, accumulate, n4, st);
+}
+
+int mmh_conv7_stem_sparse_wgrad_flat_supported(const mmh_conv_desc* d) {
+    return mmh::g_stem_sparse && mmh::g_stem_sparse_flat && wgrad_flat_ok(d) ? 1 : 0;
+}
+
+size_t mmh_conv7_stem_sparse_wgrad_flat_ws_bytes(const mmh_conv_desc* d) {
+    if (!wgrad_flat_ok(d)) return 0;
+    int splits, pps;
+    mmh::wgrad_flat_split(49 * d->Cin, 64, d->B * d->H * d->W, splits, pps);
+    return (size_t)splits * 49 * d->Cin * 64 * sizeof(float);
+}
+
+int mmh_conv7_stem_sparse_wgrad_flat(const mmh_conv_desc* d, const void* x, const void* mask, const void* dy, void* dw, void* ws,
+                                     size_t ws_bytes, int accumulate, mmh_stream_t s) {
+    MMH_REQUIRE(wgrad_flat_ok(d), "mmh_conv7_stem_sparse_wgrad_flat: needs an fp32 7x7 / stride 1 / reflect pad 3 stem, Cin %% 4 == 0 "
+                                  "<= 48, Cout == 64, H %% 8 == 0, W %% 16 == 0, B H W < 2^25");
+    MMH_REQUIRE(x && mask && dy && dw && ws && ws_bytes >= mmh_conv7_stem_sparse_wgrad_flat_ws_bytes(d),
+                "mmh_conv7_stem_sparse_wgrad_flat: bad buffers");
+    MMH_REQUIRE(((uintptr_t)x & 15) == 0 && ((uintptr_t)dy & 15) == 0 && ((uintptr_t)dw & 15) == 0 && ((uintptr_t)ws & 15) == 0 &&
+                    ((uintptr_t)mask & 7) == 0,
+                "mmh_conv7_stem_sparse_wgrad_flat: x, dy, dw, ws need 16-byte, mask 8-byte alignment");
+    FlatWgradKP p{};
+    p.x = static_cast<const float*>(x);
+    p.mask = static_cast<const unsigned long long*>(mask);
+    p.dy = static_cast<const float*>(dy);
+    p.slab = static_cast<float*>(ws);
+    p.H = d->H; p.W = d->W; p.Cin = d->Cin; p.x_cs = d->x_cs; p.y_cs = d->y_cs;
+    p.BX = d->W / BC; p.BY = d->H / BR; p.P = d->B * d->H * d->W;
+    int splits;
+    mmh::wgrad_flat_split(49 * d->Cin, 64, p.P, splits, p.pix_per_split);
+    hipStream_t st = mmh::as_stream(s);
+    hipLaunchKernelGGL(stem_sparse_wgrad_flat_kernel, dim3(splits, d->Cin / 4), dim3(256), 0, st, p);
+    if (int rc = mmh::check_launch("stem_sparse_wgrad_flat_kernel")) return rc;
     const int n4 = 49 * d->Cin * 64 / 4;
     return mmh::launch_slab_reduce(p.slab, static_cast<float*>(dw), n4, splits, accumulate, n4, st);
 }

@@ -88,6 +88,9 @@ SIGNATURES = {
     "mmh_conv7_stem_wgrad": (_i, [_DP, _vp, _vp, _vp, _vp, _sz, _i, _vp]),
     "mmh_stem_activity_bytes": (_sz, [_i, _i, _i]),
     "mmh_stem_activity": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
+    "mmh_conv7_stem_sparse_wgrad_flat_supported": (_i, [_DP]),
+    "mmh_conv7_stem_sparse_wgrad_flat_ws_bytes": (_sz, [_DP]),
+    "mmh_conv7_stem_sparse_wgrad_flat": (_i, [_DP, _vp, _vp, _vp, _vp, _vp, _sz, _i, _vp]),
     "mmh_conv7_stem_sparse_fprop_supported": (_i, [_DP]),
     "mmh_conv7_stem_sparse_fprop": (_i, [_DP, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mmh_conv7_stem_sparse_wgrad_supported": (_i, [_DP]),

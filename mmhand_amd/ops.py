@@ -554,10 +554,11 @@ def stem_mask_request(x, cout=64):
     if nbytes == 0 or Cc % 4 or not 4 <= Cc <= 48 or x.numel() >= 2 ** 31 or x.data_ptr() % 16:
         return None
     d = conv_desc(B, H, W_, Cc, cout, 7, 1, 3, True)
-    # both queries say no under "stem_sparse" 0; under "conv_levels" 2 only the wgrad takes the mask
+    # every query says no under "stem_sparse" 0; under "conv_levels" 2 only the wgrads take the mask
+    stem_route = USE_STEM_WGRAD and L.load().mmh_conv7_stem_wgrad_supported(C.byref(d))
     if not (L.load().mmh_conv7_stem_sparse_fprop_supported(C.byref(d))
-            or (USE_STEM_WGRAD and L.load().mmh_conv7_stem_wgrad_supported(C.byref(d))
-                and L.load().mmh_conv7_stem_sparse_wgrad_supported(C.byref(d)))):
+            or (stem_route and L.load().mmh_conv7_stem_sparse_wgrad_supported(C.byref(d)))
+            or (not stem_route and L.load().mmh_conv7_stem_sparse_wgrad_flat_supported(C.byref(d)))):
         return None
     mask = _stem_mask_for(x)
     if mask is not None:
@@ -1060,11 +1061,27 @@ def raw_conv_wgrad(x, dy, k, stride, pad, reflect, bf16=False, out=None):
             and L.load().mmh_conv7_stem_sparse_wgrad_supported(C.byref(d))):
         # a pose-map stem whose caller asked for an activity mask: per input channel, only the tiles that see it.  Taken only
         # where the dense route is mmh_conv7_stem_wgrad (44 lanes: the Generator's pose stem), whose tiles, splits and pixel
-        # order the sparse kernel keeps - the same dw bit for bit.  D_PB (24 lanes) stays on the generic wgrad: another order
+        # order the sparse kernel keeps - the same dw bit for bit.  D_PB (24 lanes): the flat kernel below
         ws = _ws(L.load().mmh_conv7_stem_sparse_wgrad_ws_bytes(C.byref(d)), x)
         dw = out if out is not None else _empty((k, k, Cin, Cout), x)
         L.call("mmh_conv7_stem_sparse_wgrad", C.byref(d), _ptr(x), _ptr(mask), _ptr(dy), _ptr(dw), _ptr(ws), ws.numel() * 4,
                int(out is not None), _stream())
+        _count_desc("mfma", d)
+        return dw
+    if (mask is not None and dy.is_contiguous() and x.dtype == torch.float32 and dy.dtype == torch.float32
+            and not (USE_STEM_WGRAD and L.load().mmh_conv7_stem_wgrad_supported(C.byref(d)))
+            and L.load().mmh_conv7_stem_sparse_wgrad_flat_supported(C.byref(d))):
+        # a pose-map stem whose dense route is the generic wgrad at the end of this function (D_PB, 24 lanes): that kernel's
+        # splits, 32-pixel steps and slab sum, multiplying a step only for the lanes that are active in it - the same dw bit
+        # for bit ("stem_sparse_flat" 0: the generic kernel).  Taken whenever the caller asked for a mask, however full it is:
+        # on an input with every lane dense it is the slower kernel (7.5 ms against 6.1 at B = 64, 256 x 256) - a mask is
+        # requested for pose-map stems only (networks.py, cp.pose_input), whose image lanes are 3 of 24
+        nbytes = L.load().mmh_conv7_stem_sparse_wgrad_flat_ws_bytes(C.byref(d))
+        assert nbytes == L.load().mmh_conv2d_wgrad_ws_bytes(C.byref(d))
+        ws = _ws(nbytes, x)
+        dw = out if out is not None else _empty((k, k, Cin, Cout), x)
+        L.call("mmh_conv7_stem_sparse_wgrad_flat", C.byref(d), _ptr(x), _ptr(mask), _ptr(dy), _ptr(dw), _ptr(ws),
+               ws.numel() * 4, int(out is not None), _stream())
         _count_desc("mfma", d)
         return dw
     if USE_STEM_WGRAD and not bf16 and L.load().mmh_conv7_stem_wgrad_supported(C.byref(d)):
