@@ -1075,6 +1075,32 @@ int mmh_pose_knn(const double* Fq, const int32_t* validq, int Nq, const double* 
 int mmh_pose_pair_distance(const double* Fa, const int32_t* valida, const double* Fb, const int32_t* validb, int n,
                            double* d /* [n] */, mmh_stream_t s);
 
+/* ---- depth condition rendered from the 3D joints (--depth_source joints, aug --novel) ----
+ * The pose-to-depth stage of the reference, baselines/quantitative_on_benchmarks/utils.py:113-124,142-194 (the 21 joints
+ * (u, v, depth / 700 * 255) rasterised bone by bone with a depth test), as an analytic rasteriser: every bone is a capsule
+ * of `radius` pixels whose depth runs linearly from joint to joint.  The reference's bone-id colours are not drawn.
+ *   xyz0, xyz1 float64 [N][21][3] = (u, v, z): u, v in pixels of the H x W output grid, z in depth / 700 * 255 units
+ *   radius     pixels, finite, >= 0;   bg: the z of a pixel no bone covers, finite
+ * Per sample and integer pixel (x, y) the 20 bones are walked in the order (0,1) (1,2) (2,3) (3,4) (0,5) (5,6) (6,7) (7,8)
+ * (0,9) (9,10) (10,11) (11,12) (0,13) (13,14) (14,15) (15,16) (0,17) (17,18) (18,19) (19,20); bone a -> b:
+ *   skipped if any of its six coordinates is not finite
+ *   dx = bu-au; dy = bv-av; L2 = dx*dx + dy*dy;  px = x-au; py = y-av
+ *   t = L2 > 0 ? (px*dx + py*dy) / L2 : 0;  t = t < 0 ? 0 : t;  t = t > 1 ? 1 : t      (a NaN t stays NaN and covers nothing)
+ *   cx = px - t*dx; cy = py - t*dy;  covered iff cx*cx + cy*cy <= radius*radius;  z = az + t*(bz-az)
+ * all in float64, every operation rounded on its own (no fused multiply-add), IEEE division.  D = the smallest z of the
+ * covering bones (a covering bone replaces D if it is the first, or if z < D), bg if there is none - a bone behind bg still
+ * wins over the background.  Stored: ((D / 255.0) - 0.5) / 0.5 in float64, cast to fp32 (the only rounding), in three lanes.
+ *   out_lanes 8: out = the decode passes' x_d, fp32 [N][H][W][8], in place: xyz0 -> lanes 0..2, xyz1 -> lanes 3..5.  A NULL
+ *                xyz leaves its side's lanes (and 6, 7) bit for bit; with both given all eight lanes are written with two
+ *                16-byte stores, 6 and 7 as the zeros the decode passes leave there.  At least one side.
+ *   out_lanes 4: out = fp32 [N][H][W][4] of its own from xyz0 (xyz1 NULL): lanes 0..2 the value, lane 3 zero - the layout
+ *                of x_h1 / x_h2, so the NCHW [N,3,H,W] view is a stride permutation.
+ * out 16-byte aligned.  Bones that cannot reach a workgroup's tile are culled by a bounding box grown by more than the
+ * arithmetic's rounding; the result does not depend on it.  One launch, no atomics, no workspace.  Bad arguments return
+ * non-zero before any launch.                                                                                          */
+int mmh_render_pose_depth(const double* xyz0, const double* xyz1, int N, int H, int W, double radius, double bg,
+                          float* out, int out_lanes, mmh_stream_t s);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }

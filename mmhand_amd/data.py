@@ -31,7 +31,13 @@ ops.pose_features / pose_knn / pose_pair_distance).  Both are decided once, in t
 (and flip) per epoch.  The host draws the parameters for the whole dataset from (aug_seed, epoch) (`augment_draws`), builds
 the 2x3 sampling matrices and transforms the joints in float64 (`affine_forward`, `affine_inverse`, `affine_joints`); the
 device samples through the matrix inside its decode pass (mmh_decode_inputs_affine / mmh_decode_inputs_indexed_affine).  The
-order of the batches, and with it the resident store, stays what it is: only `set_epoch`'s number reaches the draws."""
+order of the batches, and with it the resident store, stays what it is: only `set_epoch`'s number reaches the draws.
+
+`HandFolderLoader` with `opt.depth_source` = joints (--depth_source joints; the default `files` is the reference's loader): D1 /
+D2 are rendered from C1 / C2 - the joints as each path has them on the device, on the output grid - by
+ops.render_pose_depth, launched right behind the decode pass (here for the decoded form, in MMHandModel.set_input for the raw
+and resident forms).  No depth file is opened or sized: a raw batch carries img1 / img2 only, the decode pass is fed the
+colour images in the depth arguments and the render overwrites all of x_d; the resident store holds one slot per colour file."""
 import math
 import os
 import pickle
@@ -41,7 +47,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .options import check_augment, check_resize_inputs
+from .options import check_augment, check_depth_source, check_resize_inputs
 
 
 class SyntheticHandLoader:
@@ -113,13 +119,17 @@ def _batch_groups(indices, batch_size, max_batches):
     return groups[: int(min(len(groups), max_batches))]
 
 
-def resident_plan(image_source, image_target, indices, batch_size, max_batches=float("inf")):
+def resident_plan(image_source, image_target, indices, batch_size, max_batches=float("inf"), depth_source="files"):
     """Which files one rank's batches touch, and where each batch finds them: pure host code, no torch.
 
     -> (paths, table).  paths: the unique files in order of first use - every colour file and its "color" -> "depth" twin;
     a file that is source in one pair and target in another has ONE slot.  table: int32 [n_batches, batch_size, 4] = the
     slots of (img1, img2, dep1, dep2) of every sample.  A short last batch keeps its own length: its unused rows are -1 and
-    are never handed to the device (`table_lengths`), they are not padding a kernel reads."""
+    are never handed to the device (`table_lengths`), they are not padding a kernel reads.
+    depth_source "joints" (--depth_source joints): no depth path is named - `paths` holds the colour files alone and the two
+    depth columns repeat the colour slots (the decode pass reads SOMETHING there; the render overwrites what it makes of it)."""
+    if depth_source not in ("files", "joints"):
+        raise ValueError(f"resident_plan: depth_source {depth_source!r}")
     groups = _batch_groups(indices, batch_size, max_batches)
     slot, paths = {}, []
 
@@ -133,7 +143,10 @@ def resident_plan(image_source, image_target, indices, batch_size, max_batches=f
     for g, items in enumerate(groups):
         for r, item in enumerate(items):
             h1, h2 = image_source[item], image_target[item]
-            table[g, r] = [slot_of(h1), slot_of(h2), slot_of(h1.replace("color", "depth")), slot_of(h2.replace("color", "depth"))]
+            if depth_source == "joints":
+                table[g, r] = [slot_of(h1), slot_of(h2), slot_of(h1), slot_of(h2)]
+            else:
+                table[g, r] = [slot_of(h1), slot_of(h2), slot_of(h1.replace("color", "depth")), slot_of(h2.replace("color", "depth"))]
     return paths, table
 
 
@@ -383,6 +396,7 @@ class HandFolderLoader:
         ratio = getattr(opt, "augmentation_ratio", None)
         self.pairing, self.match_pool = check_pairing(opt)
         self.image_source, self.image_target = self._get_src_tgt(0.0 if ratio is None else float(ratio), data, key)
+        self._all_images, self._ratio = data, 0.0 if ratio is None else float(ratio)       # `data` is sorted by now
         self.device = device or torch.device("cuda", getattr(opt, "local_rank", 0) or 0)
         # --pairing curriculum | nearest: decided here, once (see _pair); `pair_distance` = float64 [n] in loader order, in
         # random mode computed on first access only; `pairing_fallbacks` = the targets `nearest` found no neighbour for
@@ -392,6 +406,9 @@ class HandFolderLoader:
         # and the dataset item of every loader position - the target's place in the split's sorted list, which the curriculum's
         # reordering carries along, so an item's transform does not depend on the pairing order
         self.augment = check_augment(opt)
+        # --depth_source joints: (radius, bg) of the render that replaces the depth files, None = files
+        self.render = check_depth_source(opt)
+        self.image_keys = _IMAGE_KEYS if self.render is None else _IMAGE_KEYS[:2]
         self.aug_epoch = 0
         self.aug_item = np.arange(len(self.image_target), dtype=np.int64)
         self._aug_draws = None
@@ -469,17 +486,7 @@ class HandFolderLoader:
             self.aug_item = self.aug_item[order]
             self._pair_distance = d[order]
             return
-        if self.match_pool == "train":
-            if "test" in self.root_dir:
-                raise ValueError(f"--match_pool train: {self.root_dir!r} is a 'test' directory, it has no training share")
-            if self.opt.isTrain:
-                raise ValueError("--match_pool train serves a generation split (isTrain False): a training loader's targets "
-                                 "ARE the training share (--match_pool self)")
-            pool = data[int((1 - ratio) * len(data)):]
-            if not pool:
-                raise ValueError(f"--match_pool train: --augmentation_ratio {ratio} leaves no training share in {self.root_dir!r}")
-        else:
-            pool = self.image_target
+        pool = self.match_pool_paths(self.match_pool)
         with torch.cuda.device(self.device):
             q = self._features(self.image_target)
             c = q if pool is self.image_target else self._features(pool)
@@ -488,6 +495,22 @@ class HandFolderLoader:
             idx = idx.cpu().numpy()
         self.image_source, self.pairing_fallbacks = apply_nearest(self.image_source, pool, idx)
         self._pair_distance = self._distances()
+
+    def match_pool_paths(self, match_pool):
+        """the candidates of a nearest-pose search: the loader's own targets (self; the list object itself, so callers can
+        tell) or the training share of the same root (train; the sorted list _get_src_tgt cut)"""
+        if match_pool != "train":
+            return self.image_target
+        data, ratio = self._all_images, self._ratio
+        if "test" in self.root_dir:
+            raise ValueError(f"--match_pool train: {self.root_dir!r} is a 'test' directory, it has no training share")
+        if self.opt.isTrain:
+            raise ValueError("--match_pool train serves a generation split (isTrain False): a training loader's targets "
+                             "ARE the training share (--match_pool self)")
+        pool = data[int((1 - ratio) * len(data)):]
+        if not pool:
+            raise ValueError(f"--match_pool train: --augmentation_ratio {ratio} leaves no training share in {self.root_dir!r}")
+        return pool
 
     def get_labels(self, image_path):
         *_, folder, name = image_path.split("/")
@@ -552,6 +575,10 @@ class HandFolderLoader:
         z2 = np.expand_dims(np.asarray(a2["depth"], dtype=np.float64), -1) / 700.0 * 255
         if self.augment is not None:
             return self._load_augmented(item, h_1, h_2, uv1, uv2, np.concatenate([uv1, z1], axis=-1), np.concatenate([uv2, z2], axis=-1))
+        if self.render is not None:         # --depth_source joints: two files per pair, no depth path is touched
+            read = _read_bytes if self.device_png else _read_bgr
+            return dict(img1=read(h_1), img2=read(h_2), uv1=uv1, uv2=uv2, C1=np.concatenate([uv1, z1], axis=-1),
+                        C2=np.concatenate([uv2, z2], axis=-1), H1_path=h_1, H2_path=h_2)
         if self.device_png:
             return dict(img1=_read_bytes(h_1), img2=_read_bytes(h_2), dep1=_read_bytes(h_1.replace("color", "depth")),
                         dep2=_read_bytes(h_2.replace("color", "depth")), uv1=uv1, uv2=uv2,
@@ -564,8 +591,9 @@ class HandFolderLoader:
         """load_sample under --augment_geom: the same files, untouched; the sample's two sampling matrices ride along as `xf`
         [2,6] and uv1 / uv2 / C1 / C2 leave already transformed, on the output grid"""
         read = _read_bytes if self.device_png else _read_bgr
-        s = dict(img1=read(h_1), img2=read(h_2), dep1=read(h_1.replace("color", "depth")),
-                 dep2=read(h_2.replace("color", "depth")), H1_path=h_1, H2_path=h_2)
+        s = dict(img1=read(h_1), img2=read(h_2), H1_path=h_1, H2_path=h_2)
+        if self.render is None:
+            s.update(dep1=read(h_1.replace("color", "depth")), dep2=read(h_2.replace("color", "depth")))
         src = png_size(h_1) if self.device_png else s["img1"].shape[:2]
         if src is None:
             raise ValueError(f"--augment_geom --device_png: {h_1} is not a PNG file, its size is unknown before the decode")
@@ -581,8 +609,8 @@ class HandFolderLoader:
                 self._png_sets = [PngBatchDecoder(self.device), PngBatchDecoder(self.device)]
             dec = self._png_sets[self._png_turn % 2]
             self._png_turn += 1
-            out["_png"] = (dec, dec.pack([s[k] for k in _IMAGE_KEYS for s in samples]))
-        keys = ("uv1", "uv2", "C1", "C2") if self.device_png else ("img1", "img2", "dep1", "dep2", "uv1", "uv2", "C1", "C2")
+            out["_png"] = (dec, dec.pack([s[k] for k in self.image_keys for s in samples]))
+        keys = ("uv1", "uv2", "C1", "C2") if self.device_png else self.image_keys + ("uv1", "uv2", "C1", "C2")
         for k in keys + (("xf",) if self.augment is not None else ()):
             t = torch.from_numpy(np.stack([s[k] for s in samples]))
             out[k] = t.pin_memory() if torch.cuda.is_available() else t
@@ -626,7 +654,7 @@ class HandFolderLoader:
         for i, reason in report:
             path = (hb["H1_path"] if i // B in (0, 2) else hb["H2_path"])[i % B]
             self.png_fallbacks.append((path.replace("color", "depth") if i // B >= 2 else path, reason))
-        return {k: pix[j * B:(j + 1) * B] for j, k in enumerate(_IMAGE_KEYS)}
+        return {k: pix[j * B:(j + 1) * B] for j, k in enumerate(self.image_keys)}
 
     def to_device(self, hb, fill=None):
         out = {k: (v.to(self.device, non_blocking=True) if torch.is_tensor(v) else v) for k, v in hb.items() if k != "_png"}
@@ -638,24 +666,32 @@ class HandFolderLoader:
             return out
         src = tuple(out["img1"].shape[1:3])
         dst = ops.resize_size(self.out_size, src)
+        # --depth_source joints: the colour images stand in the depth arguments, the render below overwrites what comes of it
+        dep1, dep2 = (out[k] for k in (("dep1", "dep2") if self.render is None else ("img1", "img2")))
         if "xf" in out:                     # --augment_geom: joints and C arrive transformed, on the output grid
-            xh1, xh2, xp, xd = ops.decode_inputs_affine(out["img1"], out["img2"], out["dep1"], out["dep2"], out["uv1"],
+            xh1, xh2, xp, xd = ops.decode_inputs_affine(out["img1"], out["img2"], dep1, dep2, out["uv1"],
                                                         out["uv2"], out["xf"], out_size=dst)
             c1, c2 = out["C1"], out["C2"]
         else:
-            xh1, xh2, xp, xd = ops.decode_inputs(out["img1"], out["img2"], out["dep1"], out["dep2"], out["uv1"], out["uv2"],
+            xh1, xh2, xp, xd = ops.decode_inputs(out["img1"], out["img2"], dep1, dep2, out["uv1"], out["uv2"],
                                                  out_size=dst)
             c1, c2 = (out[k] if dst is None else ops.resize_joints(out[k], src, dst) for k in ("C1", "C2"))
+        self._render(c1, c2, xd)
         v = ops.nhwc_to_nchw_view
         return {"H1": v(xh1, 3), "H2": v(xh2, 3), "P1": v(xp)[:, :21], "P2": v(xp)[:, 21:42], "D1": v(xd)[:, :3],
                 "D2": v(xd)[:, 3:6], "C1": c1, "C2": c2, "H1_path": out["H1_path"], "H2_path": out["H2_path"]}
+
+    def _render(self, c1, c2, xd):
+        """--depth_source joints: D1 / D2 of the decoded form, rendered into x_d from the batch's own C1 / C2 (one launch)"""
+        if self.render is not None:
+            ops.render_pose_depth(c1.contiguous(), c2.contiguous(), radius=self.render[0], bg=self.render[1], out=xd)
 
     # ------------------------------------------------------------------ resident dataset
     def _resident_setup(self):
         """plan, budget decision, store and tables; leaves `resident_state` "on" or "off: <reason>" (then nothing else differs
         from a loader without the flag)"""
         paths, table = resident_plan(self.image_source, self.image_target, self.indices(), self.opt.batchSize,
-                                     self.opt.max_dataset_size)
+                                     self.opt.max_dataset_size, depth_source="files" if self.render is None else "joints")
         size = png_size(paths[0]) if paths else None
         if size is None:
             state = "off: no batches" if not paths else f"off: {paths[0]} is not a PNG file"
@@ -724,7 +760,7 @@ class HandFolderLoader:
             return
         dev_slots = torch.from_numpy(np.where(fresh, slots, -1).astype(np.int32)).to(self.device)
         for j, k in enumerate(_IMAGE_KEYS):
-            if fresh[j].any():
+            if fresh[j].any():              # (--depth_source joints: the depth columns repeat the colour slots, never fresh)
                 ops.store_images(out[k].contiguous(), dev_slots[j], r["store"])
         r["filled"][slots[fresh]] = True
 
@@ -748,6 +784,7 @@ class HandFolderLoader:
             xh1, xh2, xp, xd = ops.decode_inputs_indexed_affine(rb.store, rb.idx, rb.uv, rb.xf, out_size=rb.out_size)
         else:
             xh1, xh2, xp, xd = ops.decode_inputs_indexed(rb.store, rb.idx, rb.uv_table, out_size=rb.out_size)
+        self._render(c1, c2, xd)
         v = ops.nhwc_to_nchw_view
         return {"H1": v(xh1, 3), "H2": v(xh2, 3), "P1": v(xp)[:, :21], "P2": v(xp)[:, 21:42], "D1": v(xd)[:, :3],
                 "D2": v(xd)[:, 3:6], "C1": c1, "C2": c2, "H1_path": p1, "H2_path": p2}

@@ -6,7 +6,8 @@ scores each output against its target image H2:
 
     python -m mmhand_amd.evaluate --name CKP [--checkpoints_dir checkpoints] [--which_epoch latest] --dataroot DIR
         --dataset rhd|stb [--augmentation_ratio R] [--batchSize 16] [--bf16] [--gpu 0] [--window 11]
-        [--resize_inputs N] [--pairing P [--match_pool M]] [--results_json PATH] [--per_image_csv PATH]
+        [--resize_inputs N] [--pairing P [--match_pool M]] [--depth_source files|joints [--render_radius R] [--render_bg Z]]
+        [--results_json PATH] [--per_image_csv PATH]
 
 Directory mode - scores the PNGs aug.py wrote (<DIR>/<folder of the target>/<name>) against the target colour PNGs:
 
@@ -59,6 +60,11 @@ def build_parser():
     p.add_argument("--pairing", default=None, choices=("random", "curriculum", "nearest"),
                    help="how a target gets its source (as aug's flag); given, the outputs also report the pairs' pose distance")
     p.add_argument("--match_pool", default=None, choices=("self", "train"), help="with --pairing nearest: the sources' pool")
+    p.add_argument("--depth_source", default="files", choices=("files", "joints"),
+                   help="joints: the depth conditions are rendered from the 3D joints on the device (as train's and aug's flag); "
+                        "no depth PNG is opened")
+    p.add_argument("--render_radius", type=float, default=5.0, help="with --depth_source joints: half-width of a bone, pixels")
+    p.add_argument("--render_bg", type=float, default=255.0, help="with --depth_source joints: depth where no bone covers")
     p.add_argument("--window", type=int, default=11, help="SSIM window, odd, 3 .. 15 (the reference's default 11)")
     p.add_argument("--results_json", default=None,
                    help="default: <checkpoints_dir>/<name>/eval_<which_epoch>_<dataset>.json, or <generated>/eval_<dataset>.json")
@@ -102,6 +108,8 @@ def _opt(args):
     opt.device_png = bool(getattr(args, "device_png", False))
     opt.resize_inputs = int(getattr(args, "resize_inputs", 0) or 0)
     opt.pairing, opt.match_pool = getattr(args, "pairing", None) or "random", getattr(args, "match_pool", None) or "self"
+    opt.depth_source = getattr(args, "depth_source", None) or "files"
+    opt.render_radius, opt.render_bg = float(getattr(args, "render_radius", 5.0)), float(getattr(args, "render_bg", 255.0))
     return opt
 
 
@@ -185,8 +193,9 @@ def main(argv=None):
         parser.error(f"--window {args.window}: the SSIM window is odd, from 3 to 15")
     if args.batchSize < 1:
         parser.error("--batchSize must be >= 1")
-    from .options import check_resize_inputs
+    from .options import check_depth_source, check_resize_inputs
     check_resize_inputs(args)
+    check_depth_source(args)
     ckpt = None
     if args.name:
         ckpt = os.path.join(args.checkpoints_dir, args.name, f"{args.which_epoch}_net_netG.pth")
@@ -212,6 +221,8 @@ def main(argv=None):
     with open(out, "w") as fh:
         # the pairing flags appear among the options only when --pairing was given: without it the file is what it always was
         options = {k: v for k, v in vars(args).items() if pose_d is not None or k not in ("pairing", "match_pool")}
+        if args.depth_source == "files":       # likewise the render's flags: only under --depth_source joints
+            options = {k: v for k, v in options.items() if k not in ("depth_source", "render_radius", "render_bg")}
         json.dump({"summary": summary, "options": options, "generator": config or None,
                    "domain": "[0, 1]: generator output (x + 1) / 2, PNG pixels u8 / 255"}, fh, indent=1)
     if args.per_image_csv:

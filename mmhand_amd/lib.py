@@ -218,6 +218,7 @@ SIGNATURES = {
     "mmh_pose_knn_ws_bytes": (_sz, [_i, _i, _i, _i]),
     "mmh_pose_knn": (_i, [_vp, _vp, _i, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp]),
     "mmh_pose_pair_distance": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp]),
+    "mmh_render_pose_depth": (_i, [_vp, _vp, _i, _i, _i, _d, _d, _vp, _i, _vp]),
 }
 
 _lib = None

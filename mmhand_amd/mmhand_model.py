@@ -23,7 +23,7 @@ from . import lib as L
 from . import ops
 from .networks import Discriminator, Generator, VGGHead, discriminators_lockstep
 from .ops import pad4
-from .options import check_exact_fwd, check_resize_inputs
+from .options import check_depth_source, check_exact_fwd, check_resize_inputs
 
 
 MERGE_D_PASSES = os.environ.get("MMH_MERGE_D", "1") != "0"
@@ -327,6 +327,8 @@ class MMHandModel(torch.nn.Module):
                                                and dist.is_initialized()) else 1
         check_exact_fwd(opt)
         self.resize_inputs = check_resize_inputs(opt)      # --resize_inputs N: raw batches are decoded to N x N (set_input_raw)
+        # --depth_source joints: (radius, bg) of the render that follows every decode pass here (_set_decoded), None = files
+        self.render = check_depth_source(opt, need_dataroot=False)
         if getattr(opt, "fp32_exact_grads", False):
             # process-wide, like MMH_WINOGRAD=bwd | bwd_f2 (one model family per process)
             ops.set_winograd_mode("bwd_f2" if getattr(opt, "fp32_exact_fwd", "direct") == "wino2" else "bwd")
@@ -531,17 +533,26 @@ class MMHandModel(torch.nn.Module):
             # and on the output grid, so nothing is scaled here
             aug = "xf" in input
             raw = ("img1", "img2", "dep1", "dep2", "uv1", "uv2") + (("xf",) if aug else ())
-            if any(not input[k].is_cuda for k in raw):
+            # --depth_source joints: the loader's batch carries no depth images; the colour images stand in for them in the
+            # decode pass and the render behind it (_set_decoded) overwrites D1 / D2
+            alias = {"dep1": "img1", "dep2": "img2"} if "dep1" not in input else {}
+            if alias and self.render is None:
+                raise ValueError("a raw batch without dep1 / dep2 needs --depth_source joints on the model as on the loader")
+            have = tuple(k for k in raw if k not in alias)
+            self._need_joints(input)
+            if any(not input[k].is_cuda for k in have):
                 if getattr(self, "_copy_stream", None) is None:
                     self._copy_stream = torch.cuda.Stream(dev)
                 cur = torch.cuda.current_stream(dev)
                 with torch.cuda.stream(self._copy_stream):
-                    t = {k: input[k].to(dev, non_blocking=True).contiguous() for k in raw}
+                    t = {k: input[k].to(dev, non_blocking=True).contiguous() for k in have}
                 cur.wait_stream(self._copy_stream)
                 for v in t.values():
                     v.record_stream(cur)
             else:
-                t = {k: input[k].contiguous() for k in raw}
+                t = {k: input[k].contiguous() for k in have}
+            for k, src_key in alias.items():
+                t[k] = t[src_key]
             if "C1" in input and "C2" in input:
                 # (u, v, depth) of the joints on the grid the networks see: scaled with the images under --resize_inputs
                 src, dst = tuple(t["img1"].shape[1:3]), ops.resize_size(self.resize_inputs, t["img1"].shape[1:3])
@@ -558,6 +569,7 @@ class MMHandModel(torch.nn.Module):
             # (mmh_decode_inputs_indexed) reads them by slot - no file, no PNG decode, no upload.  The tables are on the
             # output grid of the loader's --resize_inputs, which is this model's (both read the same option)
             rb = input["resident"]
+            self._need_joints(input)
             assert (rb.out_size or 0) == (self.resize_inputs or 0), \
                 f"resident batch prepared for --resize_inputs {rb.out_size or 0}, the model runs {self.resize_inputs or 0}"
             if "C1" in input and "C2" in input:
@@ -634,6 +646,7 @@ class MMHandModel(torch.nn.Module):
     def _set_decoded(self, decode, paths=None):
         """what follows the decode pass, whichever entry point ran it (`decode()` -> x_H1, x_H2, x_P, x_D): set_input_raw's
         batch-fed pass, or set_input's slot-fed one on a resident batch"""
+        decode = self._with_render(decode)
         if getattr(self, "_graph_state", "off") == "replay":
             xh1, xh2, xp, xd = decode()
             v, o = ops.nhwc_to_nchw_view, self.opt
@@ -655,6 +668,27 @@ class MMHandModel(torch.nn.Module):
         self.input_D2 = v(self.x_D)[:, o.D_input_nc: 2 * o.D_input_nc]
         if paths is not None:
             self.image_paths = paths[0][0] + "___" + paths[1][0]
+
+    def _need_joints(self, input):
+        if self.render is not None and not ("C1" in input and "C2" in input):
+            raise ValueError("--depth_source joints renders D1 / D2 from the batch's C1 / C2: the batch carries neither")
+
+    def _with_render(self, decode):
+        """--depth_source joints: the decode pass followed by ops.render_pose_depth of this batch's C1 / C2 (set_input left
+        them in input_C1 / input_C2, on the output grid) into x_d - D1 and D2 in one launch.  `files`: the decode as it is."""
+        if self.render is None:
+            return decode
+        c1, c2 = getattr(self, "input_C1", None), getattr(self, "input_C2", None)
+
+        def run():
+            xh1, xh2, xp, xd = decode()
+            if c1 is None or c2 is None or c1.shape[0] != xd.shape[0] or c2.shape[0] != xd.shape[0]:
+                raise ValueError("--depth_source joints renders D1 / D2 from the batch's C1 / C2: feed batches through set_input "
+                                 "with both keys")
+            ops.render_pose_depth(c1.to(xd.device).contiguous(), c2.to(xd.device).contiguous(), radius=self.render[0],
+                                  bg=self.render[1], out=xd)
+            return xh1, xh2, xp, xd
+        return run
 
     def forward(self):
         self.fake_nhwc = self.netG.forward_nhwc(self.x_H1, self.x_P, self.x_D)

@@ -14,6 +14,7 @@ are physical [kh, kw, Cin, Cout]; the nn.Parameter objects the modules expose
 are permuted *views* of them with the reference's logical OIHW / IOHW shape.
 """
 import ctypes as C
+import math
 import os
 import weakref
 
@@ -3498,3 +3499,38 @@ def pose_pair_distance(a, b):
     d = torch.empty((Fa.shape[0],), dtype=torch.float64, device=Fa.device)
     L.call("mmh_pose_pair_distance", _ptr(Fa), _ptr(va), _ptr(Fb), _ptr(vb), Fa.shape[0], _ptr(d), _stream())
     return d
+
+
+# ----------------------------------------------------------------------------- depth condition from the joints (csrc/render_depth.hip)
+def render_pose_depth(xyz0, xyz1=None, size=None, radius=5.0, bg=255.0, out=None):
+    """The depth condition of a 3D pose, rendered on the device (mmh_render_pose_depth; the reference's pose-to-depth stage,
+    baselines/quantitative_on_benchmarks/utils.py:113-124,142-194): xyz float64 [N,21,3] = (u, v, z) with u, v in pixels of
+    the output grid and z in C1 / C2's units (depth / 700 * 255); the 20 bones as capsules of `radius` pixels, nearest z wins,
+    `bg` where no bone covers; stored ((z / 255) - 0.5) / 0.5 as fp32.  Bit for bit tests/_render_oracle.py's float64 numpy.
+
+    out=None: a new fp32 [N,H,W,4] for size = (H, W) from xyz0 alone (lanes 0..2 the value, lane 3 zero;
+    nhwc_to_nchw_view(out, 3) is the [N,3,H,W] view).
+    out = the decode passes' x_d, fp32 [N,H,W,8]: in place, xyz0 -> lanes 0..2 (D1), xyz1 -> lanes 3..5 (D2); either may be
+    None and then its lanes are left as they are; both sides are one launch.  Returns `out`."""
+    given = [t for t in (xyz0, xyz1) if t is not None]
+    assert given, "render_pose_depth: at least one pose tensor"
+    N, dev = given[0].shape[0], given[0].device
+    for t in given:
+        assert t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and t.dim() == 3 and t.device == dev and \
+            tuple(t.shape) == (N, 21, 3) and N >= 1, "poses: contiguous float64 CUDA [N,21,3] on one device"
+    radius, bg = float(radius), float(bg)
+    if not (radius >= 0.0 and math.isfinite(radius)) or not math.isfinite(bg):
+        raise ValueError(f"render_pose_depth: radius {radius!r} (finite, >= 0), bg {bg!r} (finite)")
+    if out is None:
+        assert xyz0 is not None and xyz1 is None and size is not None, "the standalone form renders xyz0 alone at size = (H, W)"
+        H, W_ = int(size[0]), int(size[1])
+        out = torch.empty((N, H, W_, 4), dtype=torch.float32, device=dev)
+        lanes = 4
+    else:
+        assert out.dtype == torch.float32 and out.device == dev and out.is_contiguous() and out.dim() == 4 and \
+            out.shape[0] == N and out.shape[3] == 8, "out: contiguous fp32 [N,H,W,8] on the poses' device (the decode passes' x_d)"
+        H, W_ = int(out.shape[1]), int(out.shape[2])
+        assert size is None or (int(size[0]), int(size[1])) == (H, W_), "size disagrees with out"
+        lanes = 8
+    L.call("mmh_render_pose_depth", _ptr(xyz0), _ptr(xyz1), N, H, W_, radius, bg, _ptr(out), lanes, _stream())
+    return out

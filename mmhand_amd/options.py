@@ -30,7 +30,9 @@ Differences, all deliberate:
     the paper's pairing strategies on the reference's pose distance (data.HandFolderLoader, csrc/pose_knn.hip);
   * --augment_geom with --aug_rotate / --aug_scale / --aug_shift / --aug_flip / --aug_pair / --aug_seed (additions to `train`;
     off): a random affine transform per image and epoch inside the device's decode pass (data.augment_draws,
-    ops.decode_inputs_affine).  The reference declares --no_flip / --use_flip and never reads them; they stay dead here.
+    ops.decode_inputs_affine).  The reference declares --no_flip / --use_flip and never reads them; they stay dead here;
+  * --depth_source files | joints with --render_radius / --render_bg (additions; files = the reference's loader): joints
+    renders D1 / D2 from C1 / C2 on the device (ops.render_pose_depth, csrc/render_depth.hip) instead of reading depth PNGs.
 """
 import argparse
 import os
@@ -121,6 +123,17 @@ _BASE = [
     ("--match_pool", dict(type=str, default="self", choices=["self", "train"],
                           help="with --pairing nearest: where the sources come from - self: the loader's own targets, the target "
                                "itself excluded; train: the training share of the same --dataroot, for a generation split")),
+    ("--depth_source", dict(type=str, default="files", choices=["files", "joints"],
+                            help="with --dataroot: where the depth conditions D1 / D2 come from - files: the depth PNG beside "
+                                 "every colour PNG; joints: rendered on the device from the 3D joints C1 / C2 right after the "
+                                 "decode pass (mmh_render_pose_depth: 20 bones as capsules with a depth test) - no depth file "
+                                 "is opened, and --resident_dataset holds one slot per colour file")),
+    ("--render_radius", dict(type=float, default=5.0,
+                             help="with --depth_source joints: half-width of a bone in pixels of the grid the networks see; "
+                                  "like sigma it is not scaled by --resize_inputs or --augment_geom")),
+    ("--render_bg", dict(type=float, default=255.0,
+                         help="with --depth_source joints: the depth of a pixel no bone covers, in C1 / C2's units "
+                              "(depth / 700 * 255); 255 maps to +1")),
 ]
 _TRAIN = [
     ("--display_freq", dict(type=int, default=100)),
@@ -192,6 +205,33 @@ def check_resize_inputs(opt):
     return n
 
 
+DEPTH_SOURCES = ("files", "joints")
+
+
+def check_depth_source(opt, need_dataroot=True):
+    """--depth_source with --render_radius / --render_bg, validated; absent attributes are the defaults.  Returns None for
+    `files`, else (radius, bg).  need_dataroot=False: for a consumer of batches (MMHandModel), which has no loader to ask."""
+    src = getattr(opt, "depth_source", None) or "files"
+    if src not in DEPTH_SOURCES:
+        raise ValueError(f"--depth_source {src!r}: expected one of {' | '.join(DEPTH_SOURCES)}")
+
+    def num(name, default):
+        v = getattr(opt, name, default)
+        v = default if v is None else v
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or v != v or v in (float("inf"), float("-inf")):
+            raise ValueError(f"--{name} {v!r}: a finite number expected")
+        return float(v)
+
+    radius, bg = num("render_radius", 5.0), num("render_bg", 255.0)
+    if radius < 0.0:
+        raise ValueError(f"--render_radius {radius!r}: expected pixels, >= 0")
+    if src == "files":
+        return None
+    if need_dataroot and not getattr(opt, "dataroot", None):
+        raise ValueError("--depth_source joints works with --dataroot only (the synthetic loader has no joints' depth)")
+    return radius, bg
+
+
 AUG_PAIRS = ("shared", "independent")
 
 
@@ -252,6 +292,7 @@ class BaseOptions:
             self.parser.error(str(e))
         check_resize_inputs(opt)        # a ValueError, as for a namespace built in code (MMHandModel checks those)
         check_augment(opt)              # likewise (data.HandFolderLoader checks those)
+        check_depth_source(opt)         # likewise
         opt.isTrain = self.isTrain
         import torch
         if opt.distributed:

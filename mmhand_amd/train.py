@@ -11,7 +11,9 @@ batches (`--synthetic_samples N` sets the epoch length).  `--resize_inputs N` wi
 N x N whatever size the files hold - the raw batches travel at the files' size and the device's decode pass writes N x N
 (MMHandModel.set_input; synthetic batches keep `--fineSize`).  `--resident_dataset` with `--dataroot`: the decoded images stay
 in device memory after the first epoch (at most `--resident_gb` GB of it) and every later batch is one kernel
-(data.HandFolderLoader(resident=True))."""
+(data.HandFolderLoader(resident=True)).  `--depth_source joints` with `--dataroot`: the depth conditions D1 / D2 are rendered on
+the device from the 3D joints (ops.render_pose_depth) instead of read from depth PNGs - a prepared directory without depth files,
+such as the one `aug --novel` writes, trains."""
 import os
 import sys
 import time
