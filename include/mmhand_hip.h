@@ -1101,6 +1101,47 @@ int mmh_pose_pair_distance(const double* Fa, const int32_t* valida, const double
 int mmh_render_pose_depth(const double* xyz0, const double* xyz1, int N, int H, int W, double radius, double bg,
                           float* out, int out_lanes, mmh_stream_t s);
 
+/* ---- hand-pose estimators for PCK (baselines/quantitative_on_benchmarks/hpe_estimator.py:97-143, networks/net_hpm2d.py,
+ *      networks/net_hpm3d.py): the passes around their convolutions.  The convolutions themselves are mmh_conv2d_fprop
+ *      (zero padding, ReLU) and the pools mmh_maxpool2x2_fwd.                                                            */
+
+/* replaces data/RHD_dataset.py:121,215-227: cv2.normalize(img, None, alpha=1, norm_type=NORM_MINMAX, dtype=CV_32F).
+ * src: B images [3][H][W] of any mmh_image_src dtype and strides (scale / offset are not looked at: a min-max normalisation
+ * does not change under an affine map of its input, and the stored values are what is exact).  Per image mn / mx = the
+ * smallest / largest stored value over all pixels and the three channels together; out [B][H][W][4] fp32 = (float)
+ * (((double)v - mn) / ((double)mx - mn)) in lanes 0..2 in the source's channel order, 0 in lane 3; a constant image gives
+ * zeros.  One rounding: bit-identical to that expression in numpy float64.  No atomics; the partials of an image are merged
+ * in a fixed order.  ws: mmh_hpe_normalize_ws_bytes(B, H, W) bytes (0 = refused), 8-byte aligned; out 16-byte aligned.   */
+size_t mmh_hpe_normalize_ws_bytes(int B, int H, int W);
+int mmh_hpe_normalize(const mmh_image_src* src, int B, int H, int W, void* ws, size_t ws_bytes, float* out, mmh_stream_t s);
+
+/* replaces networks/net_hpm2d.py:69,118 (nn.Upsample(scale_factor=8, mode='bilinear', align_corners=True)) and
+ * hpe_estimator.py:127-135 (torch.max of every joint's map, index -> pixel).
+ * heat: fp32 [B][h][w][cs], cs >= 21, joints in lanes 0..20.  up: fp32 [B][8h][8w][24], lanes 21..23 zero (the input of
+ * Hpm3d).  For output row oy: sy = ((double)(h - 1) / (double)(8h - 1)) * oy, y0 = (int)sy, y1 = min(y0 + 1, h - 1),
+ * wy = sy - y0, columns alike; value = (float)((1 - wy) * ((1 - wx) * v00 + wx * v01) + wy * ((1 - wx) * v10 + wx * v11)),
+ * every operation in float64 and rounded on its own (no fused multiply-add), one rounding to fp32.
+ * arg [B][21][2] int32 = (x, y) of the largest of the ROUNDED fp32 values, the first one in scan order (y, then x) among
+ * equals; maxv [B][21] that value.  The reference computes y = index / H and x = index % W from the flat index, which is
+ * the same pixel for its square 256 x 256 maps; here y = index / (8w), x = index % (8w) for any shape.  Band partials
+ * merged in scan order, no atomics.  ws: mmh_heatmap_upsample_argmax_ws_bytes(B, h, w) bytes (0 = refused).            */
+size_t mmh_heatmap_upsample_argmax_ws_bytes(int B, int h, int w);
+int mmh_heatmap_upsample_argmax(const float* heat, int B, int h, int w, int cs, float* up, int32_t* arg, float* maxv, void* ws,
+                                size_t ws_bytes, mmh_stream_t s);
+
+/* replaces networks/net_hpm3d.py:60-62,110-114 (nn.Linear of the depth head on a handful of rows).
+ * y [M][N] = x [M][K] . wt [K][N] + bias [N], fp32, M <= 64, N % 4 == 0; wt is the transpose of nn.Linear's weight; bias
+ * may be NULL.  Definition of the sum, whatever the grid: the contraction is cut into mmh_linear_chunks(K) chunks of 256
+ * consecutive k; a chunk's sum is one fma chain over its k in ascending order, starting from bias[n] in chunk 0 and from 0
+ * in the others; the chunks' sums are added by the library's slab reduction, whose order depends on their number and on the
+ * option "slab_reduce_par" (which of its two kernels runs; the parallel one starts from +0, so a sum of -0.0 comes out +0.0).
+ * splits: workgroups along the contraction (<= 0: one per chunk) - it changes the schedule and not one bit of y.
+ * ws: mmh_linear_fprop_ws_bytes(M, K, N) bytes (0 = refused); wt, bias, y and ws 16-byte aligned.                       */
+int mmh_linear_chunks(int K);
+size_t mmh_linear_fprop_ws_bytes(int M, int K, int N);
+int mmh_linear_fprop(const float* x, const float* wt, const float* bias, float* y, int M, int K, int N, int splits, void* ws,
+                     size_t ws_bytes, mmh_stream_t s);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }

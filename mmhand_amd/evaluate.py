@@ -22,7 +22,21 @@ pose; with the flag given the results JSON also carries `pairing` and `pose_dist
 nearest_neighbor_search.py:68-83, mean over the scored pairs) and the per-image CSV a `pose_distance` column.  Without the
 flag both files are what they were.
 
-Both print one summary line (SSIM_avg, SSIM_std, L1_avg, PSNR_avg, n) and write it with the options used as JSON."""
+Both print one summary line (SSIM_avg, SSIM_std, L1_avg, PSNR_avg, n) and write it with the options used as JSON.
+
+`--pck --hpm2d <pth> [--hpm3d <pth>] [--pck_max 30] [--pck_steps 20]`: also the reference Evaluator's pose metric (utils.py:71-78,
+hpe_estimator.py:97-143; mmhand_amd/hpe.py): every scored image goes to the 2D hand-pose machine on the device and its joints
+are compared with the TARGET pose's labels - `pck2d_auc`, `epe2d_mean`, `epe2d_median`, `pck2d_curve` and, with `--hpm3d`, the
+same for 3D - in the summary, `epe2d` [, `epe3d`] columns in the per-image CSV.  Without `--pck` nothing of it is launched and
+both files are what they were.
+
+PCK-only mode - the colour images of a prepared directory against that directory's own labels; no generator, no pairs, no
+SSIM.  This scores `aug --novel` output (a prepared directory with annotation.pickle) and gives the estimator's own PCK on
+real images, the ceiling of the generated ones:
+
+    python -m mmhand_amd.evaluate --pck_images DIR --dataset rhd|stb --hpm2d <pth> [--hpm3d <pth>] [--batchSize 16] ...
+
+The reference ships no estimator weights: a PCK figure means what its --hpm2d / --hpm3d checkpoints mean."""
 import argparse
 import csv
 import json
@@ -45,9 +59,11 @@ def build_parser():
     src = p.add_mutually_exclusive_group(required=True)
     src.add_argument("--name", help="checkpoint name: <checkpoints_dir>/<name>/<which_epoch>_net_netG.pth")
     src.add_argument("--generated", help="directory of aug.py's output PNGs, scored instead of running a generator")
+    src.add_argument("--pck_images", help="prepared directory whose colour images are scored against its own labels: PCK only")
     p.add_argument("--checkpoints_dir", default="checkpoints")
     p.add_argument("--which_epoch", default="latest")
-    p.add_argument("--dataroot", required=True, help="prepared RHD / STB directory (annotation.pickle + PNGs)")
+    p.add_argument("--dataroot", default=None, help="prepared RHD / STB directory (annotation.pickle + PNGs); required except "
+                                                    "with --pck_images")
     p.add_argument("--dataset", required=True, choices=("rhd", "stb"))
     p.add_argument("--augmentation_ratio", type=float, default=None,
                    help="the generation split is the first (1 - ratio) share; a root with 'test' in its path serves all")
@@ -69,6 +85,11 @@ def build_parser():
     p.add_argument("--results_json", default=None,
                    help="default: <checkpoints_dir>/<name>/eval_<which_epoch>_<dataset>.json, or <generated>/eval_<dataset>.json")
     p.add_argument("--per_image_csv", default=None, help="one row per target: target, source, ssim, l1, psnr")
+    p.add_argument("--pck", action="store_true", help="also score the pose of every image with the hand-pose estimators")
+    p.add_argument("--hpm2d", default=None, help="with --pck: the 2D hand-pose machine's checkpoint (the reference's Hpm2d)")
+    p.add_argument("--hpm3d", default=None, help="with --pck: the 3D lift's checkpoint (Hpm3d); without it only 2D figures")
+    p.add_argument("--pck_max", type=float, default=30, help="largest PCK threshold in pixels (the reference's 30)")
+    p.add_argument("--pck_steps", type=int, default=20, help="number of PCK thresholds from 0 to --pck_max (the reference's 20)")
     return p
 
 
@@ -121,10 +142,37 @@ def _pose_distances(args, loader):
     return {(t, s): float(d[i]) for i, (s, t) in enumerate(zip(loader.image_source, loader.image_target))}
 
 
+PCK_FLAGS = ("pck", "pck_images", "hpm2d", "hpm3d", "pck_max", "pck_steps")
+
+
+def _estimator(args, dev):
+    """the hand-pose estimators of --pck, or None (then nothing of them is loaded or launched)"""
+    if not args.pck:
+        return None
+    from .hpe import HPEstimator, Z_SCALE
+    return HPEstimator(args.hpm2d, args.hpm3d, device=dev, z_scale=Z_SCALE[args.dataset])
+
+
+def _pose_labels(loader, paths, size=None):
+    """(uv [B,21,2], depth [B,21]) of the images' labels, float64; under --resize_inputs N the joints on the N x N grid"""
+    from . import ops
+    from .data import png_size
+    uv, depth = [], []
+    for p in paths:
+        a = loader.get_labels(p)
+        j = torch.as_tensor(np.asarray(a["uv_coord"], dtype=np.float64).reshape(21, 2))
+        if size:
+            j = ops.resize_joints(j, png_size(p), (size, size))
+        uv.append(j.numpy())
+        depth.append(np.asarray(a["depth"], dtype=np.float64).reshape(21))
+    return np.stack(uv), np.stack(depth)
+
+
 def _score_generator(args, ckpt, dev):
     from .data import HandFolderLoader
     from .inference import InferenceGenerator
     from .networks import Generator
+    est = _estimator(args, dev)
     sd = strip_module(torch.load(ckpt, map_location="cpu"))
     ngf, n_blocks, norm, use_dropout = infer_generator_config(sd)
     net = Generator(input_nc=[3, 42, 6], output_nc=3, ngf=ngf, norm_layer=norm, use_dropout=use_dropout, n_blocks=n_blocks)
@@ -135,8 +183,12 @@ def _score_generator(args, ckpt, dev):
     for s in loader:
         fake = gen([s["H1"], torch.cat((s["P1"], s["P2"]), 1), torch.cat((s["D1"], s["D2"]), 1)])
         # gen returns its graph's static output buffer: the metric is enqueued here, before the next replay
-        meter.feed(fake, s["H2"], [{"target": t, "source": h} for t, h in zip(s["H2_path"], s["H1_path"])])
-    return meter, {"ngf": ngf, "n_blocks": n_blocks, "norm": norm, "use_dropout": use_dropout}, _pose_distances(args, loader)
+        paths = [{"target": t, "source": h} for t, h in zip(s["H2_path"], s["H1_path"])]
+        meter.feed(fake, s["H2"], paths)
+        if est is not None:     # the fake batch as it lies on the device: min-max normalised by the estimator's first kernel
+            est.feed(fake, *_pose_labels(loader, s["H2_path"], loader.out_size), paths=paths)
+    return (meter, {"ngf": ngf, "n_blocks": n_blocks, "norm": norm, "use_dropout": use_dropout}, _pose_distances(args, loader),
+            est)
 
 
 def _read_generated(path):
@@ -165,6 +217,7 @@ def _score_directory(args, dev):
     # at the files' size both sides are bytes; at --resize_inputs N the targets are the decode pass's fp32 images, and the
     # PNGs' bytes are mapped to the same [-1, 1] range
     meter = QualityMeter("pm1" if size else "u8_bgr_hwc", args.window)
+    est = _estimator(args, dev)
     idx = loader.indices()
     for i in range(0, len(idx), args.batchSize):
         tgts = [loader.image_target[j] for j in idx[i:i + args.batchSize]]
@@ -175,15 +228,81 @@ def _score_directory(args, dev):
             want = (size, size, 3) if size else r.shape
             if g.shape != want:
                 raise SystemExit(f"--generated: {t}: generated image {g.shape} vs target {want}")
+        g8 = torch.from_numpy(np.stack(gen)).to(dev)
+        if est is not None:     # the PNGs' bytes, B,G,R as they were read
+            est.feed(g8, *_pose_labels(loader, tgts, size), paths=[{"target": t, "source": s} for t, s in zip(tgts, srcs)],
+                     layout="bgr_hwc")
         if size:
-            g8 = torch.from_numpy(np.stack(gen)).to(dev)
             pred = (g8.flip(-1).permute(0, 3, 1, 2).float() / 255.0 - 0.5) / 0.5
             meter.feed(pred, _targets_at(torch.from_numpy(np.stack(ref)).to(dev).contiguous(), size),
                        [{"target": t, "source": s} for t, s in zip(tgts, srcs)])
             continue
-        meter.feed(torch.from_numpy(np.stack(gen)).to(dev), torch.from_numpy(np.stack(ref)).to(dev),
+        meter.feed(g8, torch.from_numpy(np.stack(ref)).to(dev),
                    [{"target": t, "source": s} for t, s in zip(tgts, srcs)])
-    return meter, {}, _pose_distances(args, loader)
+    return meter, {}, _pose_distances(args, loader), est
+
+
+def _score_pck_images(args, dev):
+    """--pck_images: every colour image the prepared directory lists (the loader's own list and order), against its labels"""
+    from .data import HandFolderLoader, _read_bgr
+    args.dataroot = args.pck_images
+    loader = HandFolderLoader(_opt(args), device=dev)
+    est = _estimator(args, dev)
+    paths = list(loader._all_images)
+    for i in range(0, len(paths), args.batchSize):
+        chunk = paths[i:i + args.batchSize]
+        imgs = [_read_bgr(p) for p in chunk]
+        if any(im.shape != imgs[0].shape for im in imgs):
+            raise SystemExit(f"--pck_images: images of different sizes in one batch ({chunk[0]} ...)")
+        est.feed(torch.from_numpy(np.stack(imgs)).to(dev), *_pose_labels(loader, chunk), paths=[{"target": p} for p in chunk],
+                 layout="bgr_hwc")
+    return est
+
+
+def _pck_summary(args, est, summary, rows):
+    """the estimator's figures under the reference's keys (utils.py:71-73) into the summary, epe columns into the rows"""
+    res = est.results(args.pck_max, args.pck_steps)
+    for tag in ("2d", "3d"):
+        m = res["pck" + tag]
+        if m is None:
+            continue
+        summary[f"pck{tag}_auc"] = m["auc"]
+        summary[f"epe{tag}_mean"], summary[f"epe{tag}_median"] = m["epe_mean"], m["epe_median"]
+        summary[f"pck{tag}_curve"] = m["curve"]
+    summary["pck_thresholds"] = res["pck2d"]["thresholds"]
+    cols = ["epe2d"] + (["epe3d"] if res["pck3d"] is not None else [])
+    if rows is None:
+        return res["rows"], cols
+    assert len(rows) == len(res["rows"])
+    for r, e in zip(rows, res["rows"]):
+        assert r.get("target") == e.get("target"), (r, e)
+        r.update({k: e[k] for k in cols})
+    return rows, cols
+
+
+def _main_pck_images(args):
+    if not os.path.isdir(args.pck_images):
+        raise SystemExit(f"evaluate: --pck_images {args.pck_images} is not a directory")
+    torch.cuda.set_device(args.gpu)
+    dev = torch.device("cuda", args.gpu)
+    est = _score_pck_images(args, dev)
+    summary = {"n": 0}
+    rows, cols = _pck_summary(args, est, summary, None)
+    summary["n"] = len(rows)
+    print(json.dumps(summary))
+    out = args.results_json or os.path.join(args.pck_images, f"eval_pck_{args.dataset}.json")
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, "w") as fh:
+        json.dump({"summary": summary, "options": vars(args), "generator": None,
+                   "domain": "min-max normalised per image, as the reference's datasets hand real images to the estimators"},
+                  fh, indent=1)
+    if args.per_image_csv:
+        with open(args.per_image_csv, "w", newline="") as fh:
+            w = csv.writer(fh)
+            w.writerow(["target"] + cols)
+            for r in rows:
+                w.writerow([r["target"]] + [repr(r[k]) for k in cols])
+    return {"summary": summary, "rows": rows}
 
 
 def main(argv=None):
@@ -196,6 +315,16 @@ def main(argv=None):
     from .options import check_depth_source, check_resize_inputs
     check_resize_inputs(args)
     check_depth_source(args)
+    if args.pck_images:
+        args.pck = True
+    if args.pck and not args.hpm2d:
+        parser.error("--pck / --pck_images need --hpm2d <checkpoint of the 2D hand-pose machine>")
+    if args.pck and not (args.pck_max > 0 and args.pck_steps >= 2):
+        parser.error("--pck_max must be > 0 and --pck_steps >= 2")
+    if args.pck_images:
+        return _main_pck_images(args)
+    if not args.dataroot:
+        parser.error("the following arguments are required: --dataroot")
     ckpt = None
     if args.name:
         ckpt = os.path.join(args.checkpoints_dir, args.name, f"{args.which_epoch}_net_netG.pth")
@@ -205,9 +334,10 @@ def main(argv=None):
         raise SystemExit(f"evaluate: --generated {args.generated} is not a directory")
     torch.cuda.set_device(args.gpu)
     dev = torch.device("cuda", args.gpu)
-    meter, config, pose_d = _score_generator(args, ckpt, dev) if ckpt else _score_directory(args, dev)
+    meter, config, pose_d, est = _score_generator(args, ckpt, dev) if ckpt else _score_directory(args, dev)
     res = meter.result()
     summary = res["summary"]
+    pck_cols = _pck_summary(args, est, summary, res["rows"])[1] if est is not None else []
     if pose_d is not None:
         for r in res["rows"]:
             r["pose_distance"] = pose_d[(r["target"], r["source"])]
@@ -223,12 +353,14 @@ def main(argv=None):
         options = {k: v for k, v in vars(args).items() if pose_d is not None or k not in ("pairing", "match_pool")}
         if args.depth_source == "files":       # likewise the render's flags: only under --depth_source joints
             options = {k: v for k, v in options.items() if k not in ("depth_source", "render_radius", "render_bg")}
+        if est is None:                         # and the estimators' flags: only under --pck
+            options = {k: v for k, v in options.items() if k not in PCK_FLAGS}
         json.dump({"summary": summary, "options": options, "generator": config or None,
                    "domain": "[0, 1]: generator output (x + 1) / 2, PNG pixels u8 / 255"}, fh, indent=1)
     if args.per_image_csv:
         with open(args.per_image_csv, "w", newline="") as fh:
             w = csv.writer(fh)
-            extra = ["pose_distance"] if pose_d is not None else []
+            extra = (["pose_distance"] if pose_d is not None else []) + pck_cols
             w.writerow(["target", "source", "ssim", "l1", "psnr"] + extra)
             for r in res["rows"]:
                 w.writerow([r["target"], r["source"], repr(r["ssim"]), repr(r["l1"]), repr(r["psnr"])] + [repr(r[k]) for k in extra])

@@ -219,6 +219,13 @@ SIGNATURES = {
     "mmh_pose_knn": (_i, [_vp, _vp, _i, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp]),
     "mmh_pose_pair_distance": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp]),
     "mmh_render_pose_depth": (_i, [_vp, _vp, _i, _i, _i, _d, _d, _vp, _i, _vp]),
+    "mmh_hpe_normalize_ws_bytes": (_sz, [_i, _i, _i]),
+    "mmh_hpe_normalize": (_i, [C.POINTER(ImageSrc), _i, _i, _i, _vp, _sz, _vp, _vp]),
+    "mmh_heatmap_upsample_argmax_ws_bytes": (_sz, [_i, _i, _i]),
+    "mmh_heatmap_upsample_argmax": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "mmh_linear_chunks": (_i, [_i]),
+    "mmh_linear_fprop_ws_bytes": (_sz, [_i, _i, _i]),
+    "mmh_linear_fprop": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _sz, _vp]),
 }
 
 _lib = None

@@ -3534,3 +3534,78 @@ def render_pose_depth(xyz0, xyz1=None, size=None, radius=5.0, bg=255.0, out=None
         lanes = 8
     L.call("mmh_render_pose_depth", _ptr(xyz0), _ptr(xyz1), N, H, W_, radius, bg, _ptr(out), lanes, _stream())
     return out
+
+
+# ----------------------------------------------------------------------------- hand-pose estimators' passes (csrc/hpe.hip)
+_IMG_DTYPES = {torch.float32: L.F32, torch.bfloat16: L.BF16, torch.float16: L.FP16, torch.uint8: L.U8}
+
+
+def hpe_normalize(images, layout="nchw"):
+    """cv2.normalize(NORM_MINMAX, alpha=1) of every image (RHD_dataset.py:121,215-227) -> the estimators' input, fp32
+    [B,H,W,4] (lanes 0..2 the image's three channels in RGB order, lane 3 zero).  images: a CUDA tensor of any strides,
+    fp32 / bf16 / fp16 / uint8; layout "nchw": [B,3,H,W] in R,G,B order (a generator's output, or the NCHW view of an NHWC
+    buffer), "bgr_hwc": [B,H,W,3] pixels in B,G,R order as the loader reads PNGs.  Per image (x - min) / (max - min) with the
+    division in float64 and one rounding; a constant image gives zeros."""
+    if not images.is_cuda or images.dtype not in _IMG_DTYPES or images.dim() != 4:
+        raise ValueError(f"hpe_normalize: expected a 4-D fp32 / 16-bit / uint8 CUDA tensor, got {images.dtype} {tuple(images.shape)}")
+    if layout == "nchw":
+        B, Cc, H, W_ = images.shape
+        sb, sc, sh, sw = images.stride()
+        ptr = images.data_ptr()
+    elif layout == "bgr_hwc":
+        B, H, W_, Cc = images.shape
+        sb, sh, sw, sc = images.stride()
+        ptr, sc = images.data_ptr() + 2 * sc * images.element_size(), -sc
+    else:
+        raise ValueError(f"hpe_normalize: layout {layout!r}: nchw | bgr_hwc")
+    if Cc != 3:
+        raise ValueError(f"hpe_normalize: three channels expected, got {Cc}")
+    src = L.ImageSrc(ptr, _IMG_DTYPES[images.dtype], 1.0, 0.0, sb, sc, sh, sw)
+    nbytes = L.load().mmh_hpe_normalize_ws_bytes(B, H, W_)
+    if nbytes == 0:
+        raise ValueError(f"hpe_normalize: shape {tuple(images.shape)} refused")
+    ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=images.device)
+    out = torch.empty((B, H, W_, 4), dtype=torch.float32, device=images.device)
+    L.call("mmh_hpe_normalize", C.byref(src), B, H, W_, _ptr(ws), nbytes, _ptr(out), _stream())
+    return out
+
+
+def heatmap_upsample_argmax(heat):
+    """heat: fp32 [B,h,w,cs] (cs >= 21, joints in lanes 0..20) -> (up fp32 [B,8h,8w,24], xy int32 [B,21,2], peak fp32 [B,21]):
+    nn.Upsample(scale_factor=8, bilinear, align_corners=True) (net_hpm2d.py:69,118) with lanes 21..23 zero, and per joint
+    the (x, y) of the upsampled map's maximum - the first in scan order among equals - and its value
+    (hpe_estimator.py:127-135).  One pass; bit-identical to tests/_hpe_oracle.py's float64 numpy rounded once."""
+    _chk(heat, "heat")
+    if heat.dim() != 4 or heat.shape[3] < 21:
+        raise ValueError(f"heatmap_upsample_argmax: expected [B,h,w,cs >= 21], got {tuple(heat.shape)}")
+    B, h, w, cs = heat.shape
+    nbytes = L.load().mmh_heatmap_upsample_argmax_ws_bytes(B, h, w)
+    if nbytes == 0:
+        raise ValueError(f"heatmap_upsample_argmax: shape {tuple(heat.shape)} refused")
+    ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=heat.device)
+    up = _empty((B, 8 * h, 8 * w, 24), heat)
+    xy = torch.empty((B, 21, 2), dtype=torch.int32, device=heat.device)
+    peak = _empty((B, 21), heat)
+    L.call("mmh_heatmap_upsample_argmax", _ptr(heat), B, h, w, cs, _ptr(up), _ptr(xy), _ptr(peak), _ptr(ws), nbytes, _stream())
+    return up, xy, peak
+
+
+def linear(x, wt, bias=None, splits=0):
+    """y [M,N] = x [M,K] @ wt [K,N] + bias (nn.Linear with wt = weight.t().contiguous(); net_hpm3d.py:60-62,110-114), fp32,
+    M <= 64, N % 4 == 0.  splits: workgroups along K (0: one per 256-row chunk of wt); the result does not depend on it."""
+    _chk(x, "x"); _chk(wt, "wt")
+    if x.dim() != 2 or wt.dim() != 2 or x.shape[1] != wt.shape[0]:
+        raise ValueError(f"linear: x {tuple(x.shape)} @ wt {tuple(wt.shape)}")
+    M, K = x.shape
+    N = wt.shape[1]
+    if bias is not None:
+        _chk(bias, "bias")
+        if tuple(bias.shape) != (N,):
+            raise ValueError(f"linear: bias {tuple(bias.shape)} for N = {N}")
+    nbytes = L.load().mmh_linear_fprop_ws_bytes(M, K, N)
+    if nbytes == 0:
+        raise ValueError(f"linear: M={M} K={K} N={N} refused (M <= 64, N % 4 == 0)")
+    ws = _ws(nbytes, x)
+    y = _empty((M, N), x)
+    L.call("mmh_linear_fprop", _ptr(x), _ptr(wt), _ptr(bias), _ptr(y), M, K, N, int(splits), _ptr(ws), nbytes, _stream())
+    return y
