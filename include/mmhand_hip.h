@@ -1142,6 +1142,59 @@ size_t mmh_linear_fprop_ws_bytes(int M, int K, int N);
 int mmh_linear_fprop(const float* x, const float* wt, const float* bias, float* y, int M, int K, int N, int splits, void* ws,
                      size_t ws_bytes, mmh_stream_t s);
 
+/* ---- Inception score (baselines/quantitative_on_benchmarks/utils.py:12-112,196-232, inception.py): the passes around
+ *      Inception-v3's convolutions (csrc/inception.hip) and the rectangular-padding form of the fp32 forward convolution.
+ *      The fully connected layer is mmh_linear_fprop.                                                                       */
+
+/* replaces inception.py:275-282,320-321,351-357 (nn.Conv2d with kernel_size (1,7) / (7,1) / (1,3) / (3,1) and padding
+ * (0,3) / (3,0) / (0,1) / (1,0)): mmh_conv2d_fprop for fp32 and zero padding with pad_h rows above and below and pad_w
+ * columns left and right.  d->pad is not read and d->pad_mode must be MMH_PAD_ZERO; d->Ho == (H + 2 pad_h - kh) / stride + 1
+ * and d->Wo alike with pad_w.  Always the direct implicit-GEMM kernels (the option "conv_levels" holds as for
+ * mmh_conv2d_fprop), never the 7x7 stem kernel: with pad_h == pad_w == d->pad the result has the bits of mmh_conv2d_fprop
+ * wherever that runs the direct kernels itself (everything but the shapes of the fp32 7x7 stems).                         */
+int mmh_conv2d_fprop_rect(const mmh_conv_desc* d, int pad_h, int pad_w, const void* x, const void* w, const void* bias,
+                          void* y, int act, mmh_stream_t s);
+
+/* replaces utils.py:22-28 (ToPILImage, Resize(299), CenterCrop(299), ToTensor, Normalize) for a batch.
+ * src: B images [3][H][W] of any mmh_image_src dtype and strides (scale / offset are not looked at).  A stored value v that is
+ * not uint8 becomes the byte aug writes for it, ((v * 0.5f + 0.5f) * 255.0f) rounded to nearest even and clamped to 0..255, in
+ * fp32 with every operation rounded on its own; uint8 values are taken as they are.  [The reference hands ToPILImage the
+ * generator's [-1, 1] tensor, whose mul(255).byte() wraps negative values; this is the [0, 1] mapping of mmh_image_metrics.]
+ * The bytes are resized as PIL.Image.resize(BILINEAR) resizes them (ImagingResample): a horizontal pass to uint8, then a
+ * vertical pass over its result, each clip8(((1 << 21) + sum_t pixel[first + t] * coef[t]) >> 22) with an arithmetic shift.
+ * The tables are the host's (mmhand_amd/inception.py: pil_bilinear_tables), device memory:
+ *   hbounds int32 [rw][2] = (first source column, taps) of resized column j;  hcoef int32 [rw][hks], 22-bit fixed point
+ *   vbounds int32 [rh][2], vcoef int32 [rh][vks]: the same for the rows.  Indices are clamped into the image.
+ * Only the window rows crop_y .. crop_y + oh - 1 and columns crop_x .. crop_x + ow - 1 of the rh x rw resized image are
+ * produced (the centre crop).  lut fp32 [3][256] (device): channel c's value of byte u after ToTensor and Normalize.
+ * out: fp32 [B][oh][ow][4], lanes 0..2 = lut[c][byte], lane 3 zero.  Integer arithmetic and a table: bit-identical to PIL
+ * plus the table.  ws: mmh_inception_preprocess_ws_bytes(B, H, W, oh, ow) bytes (0 = refused), 4-byte aligned; out 16-byte. */
+size_t mmh_inception_preprocess_ws_bytes(int B, int H, int W, int oh, int ow);
+int mmh_inception_preprocess(const mmh_image_src* src, int B, int H, int W, const int32_t* hbounds, const int32_t* hcoef, int hks,
+                             int rw, const int32_t* vbounds, const int32_t* vcoef, int vks, int rh, int crop_y, int crop_x, int oh,
+                             int ow, const float* lut, void* ws, size_t ws_bytes, float* out, mmh_stream_t s);
+
+/* replaces inception.py:131,137,255,333 (F.max_pool2d(x, kernel_size=3, stride=2): mode MMH_POOL_MAX, no padding, output
+ * (H - 3) / 2 + 1 rows, H, W >= 3) and inception.py:225,299,379 (F.avg_pool2d(x, kernel_size=3, stride=1, padding=1): mode
+ * MMH_POOL_AVG, output H x W, the window's values inside the image summed in row-major order in fp32 and the sum divided by 9
+ * - count_include_pad - with a correctly rounded fp32 division).  x: fp32 NHWC, C lanes (C % 4 == 0) from pointer x with pixel
+ * stride x_cs; y likewise with y_cs: a pointer into a wider concat buffer writes only its own C lanes.  x, y 16-byte aligned. */
+enum { MMH_POOL_MAX = 0, MMH_POOL_AVG = 1 };
+int mmh_pool3x3_fwd(const float* x, int B, int H, int W, int C, int x_cs, float* y, int y_cs, int mode, mmh_stream_t s);
+
+/* replaces inception.py:168 (F.adaptive_avg_pool2d(x, (1, 1))): x fp32 [B][H][W] pixels of C lanes with pixel stride x_cs ->
+ * y fp32 [B][C] = (float)(sum / (H W)), the sum taken in float64 over the pixels in order.  One thread per value, no atomics. */
+int mmh_global_avgpool(const float* x, int B, int H, int W, int C, int x_cs, float* y, mmh_stream_t s);
+
+/* replaces utils.py:208-231 (F.softmax, np.mean(part, 0), scipy.stats.entropy(pyx, py) per row) for one group of n rows.
+ * logits: fp32 [n][cs], the first `classes` of each row used.  All in float64 [the reference rounds the softmax to fp32 first]:
+ * pyx = exp(l - max l) / sum, the sum a fixed tree over 256 strided partials; py [classes] = the mean of pyx over the rows in
+ * row order; kl [n] = sum_c pyx log(pyx / py), terms with pyx == 0 are 0, the same tree.  The host takes exp(mean(kl)).  The
+ * launch shapes follow from n and classes alone; no atomics.  ws: mmh_inception_score_ws_bytes(n, classes) bytes (0 = refused). */
+size_t mmh_inception_score_ws_bytes(int n, int classes);
+int mmh_inception_score(const float* logits, int n, int cs, int classes, double* kl, double* py, void* ws, size_t ws_bytes,
+                        mmh_stream_t s);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }

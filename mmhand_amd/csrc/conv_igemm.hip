@@ -2399,13 +2399,15 @@ int fprop_stats_chunks(const mmh_conv_desc* d) {
     return (int)(M / BM) * waves_m;
 }
 
+// rect_pads: {pad_h, pad_w} of mmh_conv2d_fprop_rect (then d->pad is not read and the stem kernel is not taken), else nullptr
 int do_fprop(const mmh_conv_desc* d, const void* x, const void* w, const void* bias, void* y,
-             int act, hipStream_t st, float* stats = nullptr) {
-    if (mmh::stem_f32_ok(d) && (!stats || mmh::stem_f32_stats_chunks(d) > 0))
+             int act, hipStream_t st, float* stats = nullptr, const int* rect_pads = nullptr) {
+    if (!rect_pads && mmh::stem_f32_ok(d) && (!stats || mmh::stem_f32_stats_chunks(d) > 0))
         return mmh::launch_stem_f32(d, x, w, bias, y, act, stats, st);
     ConvKP p{};
     p.stats = stats;
     p.g = fwd_gather(d, x);
+    if (rect_pads) { p.g.a0_h = -rect_pads[0]; p.g.a0_w = -rect_pads[1]; }
     set_korder(p.g, p.nk, p.Kflat);
     p.w = static_cast<const float*>(w);
     p.w_bytes = (unsigned)((size_t)d->kh * d->kw * d->Cin * d->Cout * sizeof(float));
@@ -3284,6 +3286,29 @@ int mmh_conv2d_fprop(const mmh_conv_desc* d, const void* x, const void* w, const
     if (int rc = validate(d)) return rc;
     MMH_REQUIRE(x && w && y, "mmh_conv2d_fprop: NULL buffer");
     return do_fprop(d, x, w, bias, y, act, mmh::as_stream(s));
+}
+
+int mmh_conv2d_fprop_rect(const mmh_conv_desc* d, int pad_h, int pad_w, const void* x, const void* w, const void* bias,
+                          void* y, int act, mmh_stream_t s) {
+    MMH_REQUIRE(d != nullptr, "conv desc is NULL");
+    MMH_REQUIRE(d->dtype == MMH_F32 && d->pad_mode == MMH_PAD_ZERO, "mmh_conv2d_fprop_rect: fp32 and zero padding only");
+    MMH_REQUIRE(d->Cin > 0 && d->Cout > 0 && d->Cin % 4 == 0 && d->Cout % 4 == 0, "Cin/Cout must be multiples of 4 (%d,%d)", d->Cin,
+                d->Cout);
+    MMH_REQUIRE(d->x_cs % 4 == 0 && d->y_cs % 4 == 0 && d->x_cs >= d->Cin && d->y_cs >= d->Cout,
+                "bad channel strides x_cs=%d y_cs=%d", d->x_cs, d->y_cs);
+    MMH_REQUIRE(d->stride == 1 || d->stride == 2, "stride must be 1 or 2 (%d)", d->stride);
+    MMH_REQUIRE(d->B >= 1 && d->H >= 1 && d->W >= 1 && d->kh >= 1 && d->kw >= 1 && pad_h >= 0 && pad_w >= 0 && pad_h < d->kh &&
+                    pad_w < d->kw && d->H + 2 * pad_h >= d->kh && d->W + 2 * pad_w >= d->kw,
+                "mmh_conv2d_fprop_rect: bad kernel/pad (%dx%d, pad %d,%d on %dx%d)", d->kh, d->kw, pad_h, pad_w, d->H, d->W);
+    MMH_REQUIRE(d->Ho == (d->H + 2 * pad_h - d->kh) / d->stride + 1 && d->Wo == (d->W + 2 * pad_w - d->kw) / d->stride + 1,
+                "Ho/Wo inconsistent with H,W,k,s,pad_h,pad_w");
+    MMH_REQUIRE((int64_t)d->B * (d->H + 2 * pad_h) * (d->W + 2 * pad_w) * (int64_t)d->x_cs < (1ll << 30) &&
+                    (int64_t)d->B * d->Ho * d->Wo * (int64_t)d->y_cs < (1ll << 30) &&
+                    (int64_t)d->kh * d->kw * d->Cin * d->Cout < (1ll << 30),
+                "tensor too large for 32-bit byte offsets (4 GiB per buffer)");
+    MMH_REQUIRE(x && w && y, "mmh_conv2d_fprop_rect: NULL buffer");
+    const int pads[2] = {pad_h, pad_w};
+    return do_fprop(d, x, w, bias, y, act, mmh::as_stream(s), nullptr, pads);
 }
 
 int mmh_conv2d_fprop_stats_chunks(const mmh_conv_desc* d) { return d ? fprop_stats_chunks(d) : 0; }

@@ -36,7 +36,20 @@ real images, the ceiling of the generated ones:
 
     python -m mmhand_amd.evaluate --pck_images DIR --dataset rhd|stb --hpm2d <pth> [--hpm3d <pth>] [--batchSize 16] ...
 
-The reference ships no estimator weights: a PCK figure means what its --hpm2d / --hpm3d checkpoints mean."""
+The reference ships no estimator weights: a PCK figure means what its --hpm2d / --hpm3d checkpoints mean.
+
+`--inception <pth> [--is_group 64]`: also the reference Evaluator's Inception score (utils.py:81-98,196-232; mmhand_amd/
+inception.py): every scored image becomes the bytes `aug` writes for it, is resized to 299 as PIL resizes and goes through
+Inception-v3 on the device; the logits are scored in consecutive groups of --is_group images (a tail group on its own) -
+`IS_avg`, `IS_std` (the reference's keys: mean and standard deviation over the groups), `IS_all` (one group over every image)
+and `is_groups` in the summary, an `is_kl` column in the per-image CSV.  <pth> is torchvision's inception_v3_google state dict.
+Without `--inception` nothing of it is launched and both files are what they were.
+
+IS-only mode - every PNG below a directory, no labels, no pairs; on real images this is the ceiling row of the paper's table:
+
+    python -m mmhand_amd.evaluate --is_images DIR --inception <pth> [--is_group 64] [--batchSize 16] ...
+
+No Inception weights ship with this repository or the reference: a score means what its --inception file means."""
 import argparse
 import csv
 import json
@@ -60,11 +73,12 @@ def build_parser():
     src.add_argument("--name", help="checkpoint name: <checkpoints_dir>/<name>/<which_epoch>_net_netG.pth")
     src.add_argument("--generated", help="directory of aug.py's output PNGs, scored instead of running a generator")
     src.add_argument("--pck_images", help="prepared directory whose colour images are scored against its own labels: PCK only")
+    src.add_argument("--is_images", help="directory whose PNGs (at any depth) get an Inception score: no labels, IS only")
     p.add_argument("--checkpoints_dir", default="checkpoints")
     p.add_argument("--which_epoch", default="latest")
     p.add_argument("--dataroot", default=None, help="prepared RHD / STB directory (annotation.pickle + PNGs); required except "
                                                     "with --pck_images")
-    p.add_argument("--dataset", required=True, choices=("rhd", "stb"))
+    p.add_argument("--dataset", default=None, choices=("rhd", "stb"), help="required except with --is_images")
     p.add_argument("--augmentation_ratio", type=float, default=None,
                    help="the generation split is the first (1 - ratio) share; a root with 'test' in its path serves all")
     p.add_argument("--batchSize", type=int, default=16)
@@ -90,6 +104,8 @@ def build_parser():
     p.add_argument("--hpm3d", default=None, help="with --pck: the 3D lift's checkpoint (Hpm3d); without it only 2D figures")
     p.add_argument("--pck_max", type=float, default=30, help="largest PCK threshold in pixels (the reference's 30)")
     p.add_argument("--pck_steps", type=int, default=20, help="number of PCK thresholds from 0 to --pck_max (the reference's 20)")
+    p.add_argument("--inception", default=None, help="also the Inception score: torchvision's inception_v3_google state dict")
+    p.add_argument("--is_group", type=int, default=64, help="with --inception: images per scored group (the reference's 64)")
     return p
 
 
@@ -153,6 +169,17 @@ def _estimator(args, dev):
     return HPEstimator(args.hpm2d, args.hpm3d, device=dev, z_scale=Z_SCALE[args.dataset])
 
 
+IS_FLAGS = ("inception", "is_group", "is_images")
+
+
+def _scorer(args, dev):
+    """the Inception scorer of --inception, or None (then nothing of it is loaded or launched)"""
+    if not args.inception:
+        return None
+    from .inception import InceptionScorer
+    return InceptionScorer(args.inception, group=args.is_group, device=dev)
+
+
 def _pose_labels(loader, paths, size=None):
     """(uv [B,21,2], depth [B,21]) of the images' labels, float64; under --resize_inputs N the joints on the N x N grid"""
     from . import ops
@@ -172,7 +199,7 @@ def _score_generator(args, ckpt, dev):
     from .data import HandFolderLoader
     from .inference import InferenceGenerator
     from .networks import Generator
-    est = _estimator(args, dev)
+    est, isc = _estimator(args, dev), _scorer(args, dev)
     sd = strip_module(torch.load(ckpt, map_location="cpu"))
     ngf, n_blocks, norm, use_dropout = infer_generator_config(sd)
     net = Generator(input_nc=[3, 42, 6], output_nc=3, ngf=ngf, norm_layer=norm, use_dropout=use_dropout, n_blocks=n_blocks)
@@ -187,8 +214,10 @@ def _score_generator(args, ckpt, dev):
         meter.feed(fake, s["H2"], paths)
         if est is not None:     # the fake batch as it lies on the device: min-max normalised by the estimator's first kernel
             est.feed(fake, *_pose_labels(loader, s["H2_path"], loader.out_size), paths=paths)
+        if isc is not None:     # likewise: the scorer's first kernel turns the tensor into the bytes aug would write
+            isc.feed(fake, "nchw", paths)
     return (meter, {"ngf": ngf, "n_blocks": n_blocks, "norm": norm, "use_dropout": use_dropout}, _pose_distances(args, loader),
-            est)
+            est, isc)
 
 
 def _read_generated(path):
@@ -217,7 +246,7 @@ def _score_directory(args, dev):
     # at the files' size both sides are bytes; at --resize_inputs N the targets are the decode pass's fp32 images, and the
     # PNGs' bytes are mapped to the same [-1, 1] range
     meter = QualityMeter("pm1" if size else "u8_bgr_hwc", args.window)
-    est = _estimator(args, dev)
+    est, isc = _estimator(args, dev), _scorer(args, dev)
     idx = loader.indices()
     for i in range(0, len(idx), args.batchSize):
         tgts = [loader.image_target[j] for j in idx[i:i + args.batchSize]]
@@ -232,6 +261,8 @@ def _score_directory(args, dev):
         if est is not None:     # the PNGs' bytes, B,G,R as they were read
             est.feed(g8, *_pose_labels(loader, tgts, size), paths=[{"target": t, "source": s} for t, s in zip(tgts, srcs)],
                      layout="bgr_hwc")
+        if isc is not None:
+            isc.feed(g8, "bgr_hwc", [{"target": t, "source": s} for t, s in zip(tgts, srcs)])
         if size:
             pred = (g8.flip(-1).permute(0, 3, 1, 2).float() / 255.0 - 0.5) / 0.5
             meter.feed(pred, _targets_at(torch.from_numpy(np.stack(ref)).to(dev).contiguous(), size),
@@ -239,7 +270,63 @@ def _score_directory(args, dev):
             continue
         meter.feed(g8, torch.from_numpy(np.stack(ref)).to(dev),
                    [{"target": t, "source": s} for t, s in zip(tgts, srcs)])
-    return meter, {}, _pose_distances(args, loader), est
+    return meter, {}, _pose_distances(args, loader), est, isc
+
+
+def _is_summary(isc, summary, rows):
+    """the scorer's figures into the summary (IS_avg / IS_std are the reference's keys, utils.py:67-68), is_kl into the rows"""
+    res = isc.results()
+    summary["IS_avg"], summary["IS_std"], summary["IS_all"] = res["IS_avg"], res["IS_std"], res["IS_all"]
+    summary["is_groups"] = res["n_groups"]
+    if rows is None:
+        return res["rows"]
+    assert len(rows) == len(res["rows"])
+    for r, e in zip(rows, res["rows"]):
+        assert r.get("target") == e.get("target"), (r, e)
+        r["is_kl"] = e["is_kl"]
+    return rows
+
+
+def _main_is_images(args):
+    """--is_images: every PNG below the directory in sorted order, batched while the size stays the same"""
+    from .data import _read_bgr
+    if not os.path.isdir(args.is_images):
+        raise SystemExit(f"evaluate: --is_images {args.is_images} is not a directory")
+    paths = sorted(os.path.join(d, f) for d, _, fs in os.walk(args.is_images) for f in fs if f.lower().endswith(".png"))
+    if not paths:
+        raise SystemExit(f"evaluate: --is_images {args.is_images} holds no PNG")
+    torch.cuda.set_device(args.gpu)
+    dev = torch.device("cuda", args.gpu)
+    isc = _scorer(args, dev)
+    batch = []
+
+    def flush():
+        if batch:
+            isc.feed(torch.from_numpy(np.stack([im for _, im in batch])).to(dev), "bgr_hwc", [{"target": p} for p, _ in batch])
+            batch.clear()
+
+    for p in paths:
+        im = _read_bgr(p)
+        if batch and (len(batch) == args.batchSize or batch[0][1].shape != im.shape):
+            flush()
+        batch.append((p, im))
+    flush()
+    summary = {"n": len(paths)}
+    rows = _is_summary(isc, summary, None)
+    print(json.dumps(summary))
+    out = args.results_json or os.path.join(args.is_images, "eval_is.json")
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, "w") as fh:
+        json.dump({"summary": summary, "options": vars(args), "generator": None,
+                   "domain": "the PNGs' bytes, resized to 299 as PIL.Image.resize(BILINEAR), centre crop, ImageNet normalisation"},
+                  fh, indent=1)
+    if args.per_image_csv:
+        with open(args.per_image_csv, "w", newline="") as fh:
+            w = csv.writer(fh)
+            w.writerow(["target", "is_kl"])
+            for r in rows:
+                w.writerow([r["target"], repr(r["is_kl"])])
+    return {"summary": summary, "rows": rows}
 
 
 def _score_pck_images(args, dev):
@@ -293,7 +380,7 @@ def _main_pck_images(args):
     out = args.results_json or os.path.join(args.pck_images, f"eval_pck_{args.dataset}.json")
     os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
     with open(out, "w") as fh:
-        json.dump({"summary": summary, "options": vars(args), "generator": None,
+        json.dump({"summary": summary, "options": {k: v for k, v in vars(args).items() if k not in IS_FLAGS}, "generator": None,
                    "domain": "min-max normalised per image, as the reference's datasets hand real images to the estimators"},
                   fh, indent=1)
     if args.per_image_csv:
@@ -321,6 +408,14 @@ def main(argv=None):
         parser.error("--pck / --pck_images need --hpm2d <checkpoint of the 2D hand-pose machine>")
     if args.pck and not (args.pck_max > 0 and args.pck_steps >= 2):
         parser.error("--pck_max must be > 0 and --pck_steps >= 2")
+    if args.is_images and not args.inception:
+        parser.error("--is_images needs --inception <torchvision's inception_v3_google state dict>")
+    if args.inception and args.is_group < 1:
+        parser.error("--is_group must be >= 1")
+    if args.is_images:
+        return _main_is_images(args)
+    if not args.dataset:
+        parser.error("the following arguments are required: --dataset")
     if args.pck_images:
         return _main_pck_images(args)
     if not args.dataroot:
@@ -334,10 +429,13 @@ def main(argv=None):
         raise SystemExit(f"evaluate: --generated {args.generated} is not a directory")
     torch.cuda.set_device(args.gpu)
     dev = torch.device("cuda", args.gpu)
-    meter, config, pose_d, est = _score_generator(args, ckpt, dev) if ckpt else _score_directory(args, dev)
+    meter, config, pose_d, est, isc = _score_generator(args, ckpt, dev) if ckpt else _score_directory(args, dev)
     res = meter.result()
     summary = res["summary"]
     pck_cols = _pck_summary(args, est, summary, res["rows"])[1] if est is not None else []
+    if isc is not None:
+        _is_summary(isc, summary, res["rows"])
+        pck_cols = pck_cols + ["is_kl"]
     if pose_d is not None:
         for r in res["rows"]:
             r["pose_distance"] = pose_d[(r["target"], r["source"])]
@@ -355,6 +453,8 @@ def main(argv=None):
             options = {k: v for k, v in options.items() if k not in ("depth_source", "render_radius", "render_bg")}
         if est is None:                         # and the estimators' flags: only under --pck
             options = {k: v for k, v in options.items() if k not in PCK_FLAGS}
+        if isc is None:                         # and the Inception score's: only under --inception
+            options = {k: v for k, v in options.items() if k not in IS_FLAGS}
         json.dump({"summary": summary, "options": options, "generator": config or None,
                    "domain": "[0, 1]: generator output (x + 1) / 2, PNG pixels u8 / 255"}, fh, indent=1)
     if args.per_image_csv:

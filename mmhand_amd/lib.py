@@ -16,6 +16,7 @@ PAD_ZERO, PAD_REFLECT = 0, 1
 ACT_NONE, ACT_RELU, ACT_TANH = 0, 1, 2
 F32, BF16, FP16 = 0, 1, 2
 U8 = 3          # mmh_image_src only
+POOL_MAX, POOL_AVG = 0, 1
 
 
 class ConvDesc(C.Structure):
@@ -226,6 +227,14 @@ SIGNATURES = {
     "mmh_linear_chunks": (_i, [_i]),
     "mmh_linear_fprop_ws_bytes": (_sz, [_i, _i, _i]),
     "mmh_linear_fprop": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _sz, _vp]),
+    "mmh_conv2d_fprop_rect": (_i, [_DP, _i, _i, _vp, _vp, _vp, _vp, _i, _vp]),
+    "mmh_inception_preprocess_ws_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "mmh_inception_preprocess": (_i, [C.POINTER(ImageSrc), _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp,
+                                      _vp, _sz, _vp, _vp]),
+    "mmh_pool3x3_fwd": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _i, _vp]),
+    "mmh_global_avgpool": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "mmh_inception_score_ws_bytes": (_sz, [_i, _i]),
+    "mmh_inception_score": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None

@@ -3609,3 +3609,120 @@ def linear(x, wt, bias=None, splits=0):
     y = _empty((M, N), x)
     L.call("mmh_linear_fprop", _ptr(x), _ptr(wt), _ptr(bias), _ptr(y), M, K, N, int(splits), _ptr(ws), nbytes, _stream())
     return y
+
+
+# ----------------------------------------------------------------------------- Inception score passes (csrc/inception.hip)
+def _image_src(images, layout, what):
+    """(L.ImageSrc, B, H, W) of a batch of three-channel images: layout "nchw" [B,3,H,W] in R,G,B order, "bgr_hwc" [B,H,W,3]
+    pixels in B,G,R order (read as R,G,B through a negative channel stride); any strides, fp32 / bf16 / fp16 / uint8"""
+    if not images.is_cuda or images.dtype not in _IMG_DTYPES or images.dim() != 4:
+        raise ValueError(f"{what}: expected a 4-D fp32 / 16-bit / uint8 CUDA tensor, got {images.dtype} {tuple(images.shape)}")
+    if layout == "nchw":
+        B, Cc, H, W_ = images.shape
+        sb, sc, sh, sw = images.stride()
+        ptr = images.data_ptr()
+    elif layout == "bgr_hwc":
+        B, H, W_, Cc = images.shape
+        sb, sh, sw, sc = images.stride()
+        ptr, sc = images.data_ptr() + 2 * sc * images.element_size(), -sc
+    else:
+        raise ValueError(f"{what}: layout {layout!r}: nchw | bgr_hwc")
+    if Cc != 3:
+        raise ValueError(f"{what}: three channels expected, got {Cc}")
+    return L.ImageSrc(ptr, _IMG_DTYPES[images.dtype], 1.0, 0.0, sb, sc, sh, sw), B, H, W_
+
+
+def conv_fprop_direct(x, w, bias, pad_h, pad_w, stride=1, act=L.ACT_NONE, x_off=0, out=None, y_off=0, rect=True):
+    """One fp32 zero-padded forward convolution on the direct implicit-GEMM kernels, reading and writing lane windows.
+    x fp32 [B,H,W,x_cs]: lanes x_off .. x_off + Cin are read; w fp32 RSCK [kh,kw,Cin,Cout]; bias [Cout] or None.
+    out None: a new [B,Ho,Wo,Cout]; else fp32 [B,Ho,Wo,y_cs] whose lanes y_off .. y_off + Cout are written and no other.
+    rect True: mmh_conv2d_fprop_rect with (pad_h, pad_w) (nn.Conv2d(kernel_size=(kh, kw), padding=(pad_h, pad_w)),
+    inception.py:275-282); False: mmh_conv2d_fprop, which has one padding for both axes (pad_h == pad_w)."""
+    _chk(x, "x"); _chk(w, "w")
+    B, H, W_, x_cs = x.shape
+    kh, kw, cin, cout = w.shape
+    Ho, Wo = (H + 2 * pad_h - kh) // stride + 1, (W_ + 2 * pad_w - kw) // stride + 1
+    if x_off % 4 or y_off % 4 or x_off + cin > x_cs or Ho < 1 or Wo < 1:
+        raise ValueError(f"conv_fprop_direct: x {tuple(x.shape)} lanes {x_off}+{cin}, w {tuple(w.shape)}, pad ({pad_h},{pad_w})")
+    if out is None:
+        out = _empty((B, Ho, Wo, cout), x)
+    _chk(out, "out")
+    if tuple(out.shape[:3]) != (B, Ho, Wo) or y_off + cout > out.shape[3]:
+        raise ValueError(f"conv_fprop_direct: out {tuple(out.shape)} for [{B},{Ho},{Wo}] lanes {y_off}+{cout}")
+    if bias is not None:
+        _chk(bias, "bias")
+    d = L.ConvDesc(B, H, W_, cin, cout, kh, kw, stride, pad_h, L.PAD_ZERO, Ho, Wo, x_cs, out.shape[3], L.F32)
+    xp, yp = C.c_void_p(x.data_ptr() + 4 * x_off), C.c_void_p(out.data_ptr() + 4 * y_off)
+    if rect:
+        L.call("mmh_conv2d_fprop_rect", C.byref(d), pad_h, pad_w, xp, _ptr(w), _ptr(bias), yp, act, _stream())
+    else:
+        if pad_h != pad_w:
+            raise ValueError("conv_fprop_direct: mmh_conv2d_fprop has one padding for both axes")
+        L.call("mmh_conv2d_fprop", C.byref(d), xp, _ptr(w), _ptr(bias), yp, act, _stream())
+    return out
+
+
+def inception_preprocess(images, layout, tables):
+    """utils.py:22-28 for a batch: bytes as aug writes them -> PIL's bilinear resize -> centre crop -> ToTensor -> Normalize,
+    fp32 [B,oh,ow,4] with lane 3 zero.  images / layout as _image_src; tables: mmhand_amd.inception.PreprocessTables for this
+    image size, on the images' device.  Bit-identical to PIL plus the table (integer arithmetic throughout)."""
+    src, B, H, W_ = _image_src(images, layout, "inception_preprocess")
+    t = tables
+    if (H, W_) != (t.H, t.W):
+        raise ValueError(f"inception_preprocess: tables of a {t.H} x {t.W} image for {H} x {W_}")
+    nbytes = L.load().mmh_inception_preprocess_ws_bytes(B, H, W_, t.oh, t.ow)
+    if nbytes == 0:
+        raise ValueError(f"inception_preprocess: shape {tuple(images.shape)} refused")
+    ws = torch.empty((nbytes + 3) // 4, dtype=torch.int32, device=images.device)
+    out = torch.empty((B, t.oh, t.ow, 4), dtype=torch.float32, device=images.device)
+    L.call("mmh_inception_preprocess", C.byref(src), B, H, W_, _ptr(t.hbounds), _ptr(t.hcoef), t.hks, t.rw, _ptr(t.vbounds),
+           _ptr(t.vcoef), t.vks, t.rh, t.crop_y, t.crop_x, t.oh, t.ow, _ptr(t.lut), _ptr(ws), nbytes, _ptr(out), _stream())
+    return out
+
+
+def pool3x3(x, mode, c=None, x_off=0, out=None, y_off=0):
+    """mode "max": F.max_pool2d(x, 3, 2) (inception.py:131,137,255,333); "avg": F.avg_pool2d(x, 3, 1, 1), always / 9
+    (inception.py:225,299,379).  x fp32 [B,H,W,x_cs], lanes x_off .. x_off + c (default all); out None: a new [B,Ho,Wo,c], else
+    lanes y_off .. y_off + c of out [B,Ho,Wo,y_cs] are written and no other."""
+    _chk(x, "x")
+    B, H, W_, x_cs = x.shape
+    c = x_cs - x_off if c is None else c
+    m = {"max": L.POOL_MAX, "avg": L.POOL_AVG}[mode]
+    Ho, Wo = ((H - 3) // 2 + 1, (W_ - 3) // 2 + 1) if mode == "max" else (H, W_)
+    if x_off % 4 or y_off % 4 or c % 4 or x_off + c > x_cs or Ho < 1 or Wo < 1:
+        raise ValueError(f"pool3x3 {mode}: x {tuple(x.shape)} lanes {x_off}+{c}")
+    if out is None:
+        out = _empty((B, Ho, Wo, c), x)
+    _chk(out, "out")
+    if tuple(out.shape[:3]) != (B, Ho, Wo) or y_off + c > out.shape[3]:
+        raise ValueError(f"pool3x3: out {tuple(out.shape)} for [{B},{Ho},{Wo}] lanes {y_off}+{c}")
+    L.call("mmh_pool3x3_fwd", C.c_void_p(x.data_ptr() + 4 * x_off), B, H, W_, c, x_cs, C.c_void_p(out.data_ptr() + 4 * y_off),
+           out.shape[3], m, _stream())
+    return out
+
+
+def global_avgpool(x):
+    """F.adaptive_avg_pool2d(x, (1, 1)) (inception.py:168): fp32 [B,H,W,C] -> [B,C], float64 accumulation in pixel order"""
+    _chk(x, "x")
+    B, H, W_, c = x.shape
+    y = _empty((B, c), x)
+    L.call("mmh_global_avgpool", _ptr(x), B, H, W_, c, c, _ptr(y), _stream())
+    return y
+
+
+def inception_score(logits, classes=None):
+    """utils.py:208-231 for one group: logits fp32 [n,cs] -> (kl float64 [n], py float64 [classes]) on the device; the group's
+    score is exp(mean(kl)).  float64 throughout."""
+    _chk(logits, "logits")
+    if logits.dim() != 2:
+        raise ValueError(f"inception_score: logits {tuple(logits.shape)}")
+    n, cs = logits.shape
+    classes = cs if classes is None else int(classes)
+    nbytes = L.load().mmh_inception_score_ws_bytes(n, classes)
+    if nbytes == 0 or classes > cs:
+        raise ValueError(f"inception_score: n={n} cs={cs} classes={classes} refused")
+    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=logits.device)
+    kl = torch.empty(n, dtype=torch.float64, device=logits.device)
+    py = torch.empty(classes, dtype=torch.float64, device=logits.device)
+    L.call("mmh_inception_score", _ptr(logits), n, cs, classes, _ptr(kl), _ptr(py), _ptr(ws), nbytes, _stream())
+    return kl, py
