@@ -890,7 +890,7 @@ class MMHandModel(torch.nn.Module):
         """models/MMHandModel.py:310-330: one G step, DG_ratio D_PP steps, DG_ratio D_PB steps, each
         optimizer step skipped once a gradient of the iteration was not finite."""
         self._settle_overflow()
-        ops.lp_grads_reset()
+        ops.handover_reset()
         if self.dp:
             self._optimize_parameters_dp()
         elif self.graph_step:
@@ -977,7 +977,7 @@ class MMHandModel(torch.nn.Module):
                 torch.cuda.synchronize()
                 for pool in (self.fake_PP_pool, self.fake_PB_pool):
                     pool.begin_iteration(B, self.device, decide=False)     # the decisions already drawn for this iteration
-                ops.lp_grads_reset()
+                ops.handover_reset()
         self._graph_body()
 
     def _replayed(self):
@@ -1002,7 +1002,7 @@ class MMHandModel(torch.nn.Module):
         self.fake_nhwc = self.fake_p2 = None
         self.loss_G_L1 = self.loss_G_GAN_PB = self.loss_G_GAN_PP = None
         self._fake_cats = None
-        ops.lp_grads_reset()
+        ops.handover_reset()
         gc.collect()
         self._static_inputs = {k: getattr(self, k) for k in ("input_H1", "input_P1", "input_D1", "input_H2", "input_P2",
                                                              "input_D2", "x_H1", "x_P", "x_D", "x_H2")}

@@ -21,6 +21,23 @@ import weakref
 import torch
 
 from . import lib as L
+from .handover import Handover
+
+# Values that travel beside the autograd edges, under a tensor's address (handover.py states when an entry is valid):
+# who leaves -> who takes | what empties the table.  handover_reset() runs at the start of every training iteration.
+_pending_stats = Handover("pending_stats", 8)       # conv epilogue / Winograd output transform -> the norm | reset, bump_weights_epoch
+# stem_mask_request -> the 7x7 stem's fprop and wgrad | stem_mask_forget only
+_stem_masks = Handover("stem_masks", 8, evict_live=False, same=lambda t: t.is_cuda and torch.cuda.is_current_stream_capturing())
+_nbr_sites = Handover("nbr_sites", 8, same=id)      # norm forward -> the 3x3 conv that consumes this very object | reset
+_pack_twins = Handover("pack_twins", 16, held=True)             # raw_pack / the model -> lp16_pad8 | reset (not the kept), pack_twin_drop
+_lp_grads = Handover("lp_grads", held=True)         # backward producer -> consumer, under a fresh proxy; once, a miss raises | reset
+_nb_defer = Handover("nb_defer", held=True)         # NormActFn.backward -> Conv2dFn.backward, likewise | reset
+
+
+def handover_reset():
+    """drop what a forward or backward pass that did not finish left behind"""
+    for t in (_lp_grads, _nb_defer, _nbr_sites, _pending_stats, _pack_twins):
+        t.clear(kept=True)              # (kept: the twins of model inputs, pack_twin_drop)
 
 
 def _ptr(t):
@@ -486,62 +503,33 @@ FUSE_NORM_STATS = os.environ.get("MMH_FUSE_NORM_STATS", "1") != "0"
 # (tools/ab_step.py ops:FUSE_NORM_STATS_NARROW): at 64 / 128 channels the statistics pass they save (33-59 us) costs less
 # than the epilogue arithmetic on kernels that hold one or two workgroups per CU.  Off by default.
 FUSE_NORM_STATS_NARROW = os.environ.get("MMH_FUSE_NORM_STATS_NARROW", "0") == "1"
-_pending_stats = {}
 
 
 def _park_stats(y, stats):
-    """Partial statistics of a conv output y, left for the norm that reads y next (raw_norm_stats[_finalize_pending]).
-    A conv asks for them only when its output goes straight into a norm (to_norm), so an entry lives until that norm
-    takes it - the three generator streams run conv, conv, conv, norm, norm, norm under SyncBN packing - and every
-    optimizer step / epoch bump empties the table, so no entry outlives its iteration.  The key is the output's address
-    and shape; the table is kept tiny (a conv whose norm never came would otherwise leave an entry behind)."""
-    if len(_pending_stats) >= 8:
-        _pending_stats.clear()
-    _pending_stats[y.data_ptr()] = (stats, tuple(y.shape), weakref.ref(y), y._version)
+    """Partial statistics of a conv output y, left for the norm that reads y next (raw_norm_stats[_finalize_pending]) - but
+    not at once: the three generator streams run conv, conv, conv, norm, norm, norm under SyncBN packing."""
+    _pending_stats.put(y, (stats,))
 
 
 def _take_stats(x, peek=False):
-    """the partials parked for the tensor that still lives at x's address (not for a dead conv output whose address the
-    caching allocator handed to a new tensor: the producing conv's norm may never have run), else None"""
-    pend = _pending_stats.get(x.data_ptr())
-    if pend is None:
-        return None
-    y = pend[2]()
-    if pend[1] != tuple(x.shape) or y is None or y._version != pend[3] or x._version != pend[3]:
-        del _pending_stats[x.data_ptr()]
-        return None
-    if not peek:
-        del _pending_stats[x.data_ptr()]
-    return pend
+    """(the partials,) parked for this very tensor - not for a dead conv output whose address it got - else None"""
+    return _pending_stats.get(x, pop=not peek)
 
 
 # Activity masks of the fp32 7x7 stems whose input is mostly pose heat maps (stem_sparse.hip): one uint64 per 8 x 16 pixel
 # block, bit c = "channel c is not all zero in the block and its halo".  A caller that knows its tensor is such an input (the
 # Generator's pose stem, D_PB: networks.py) asks for the mask with stem_mask_request; the stem's fprop and wgrad then find it
-# under the tensor's address, as the norm finds _pending_stats.  An entry is valid for the tensor object it was made from, at
-# the version it was made from (an in-place write - a new batch copied into a captured iteration's static buffer - makes a
-# new mask), and only on the side of a graph capture it was made on: a mask computed eagerly is never baked into a captured
-# iteration (the replay would read it for every later batch), the capture launches its own mask pass and replays it.
-_stem_masks = {}
+# under the tensor's address (_stem_masks).  An in-place write - a new batch copied into a captured iteration's static buffer -
+# makes a new mask, and a mask computed eagerly is never baked into a captured iteration (the replay would read it for every
+# later batch): the capture launches its own mask pass and replays it.  The table never evicts a live mask: it is still owed
+# to its stem's wgrad (the dense kernel takes five times as long, and that would depend on what else happened to be cached).
+_stem_mask_for = _stem_masks.get        # (masks are put with keep=True: found every time)
 
 
-def _stem_mask_for(x):
-    """the mask requested for this very tensor (address, shape, version, same side of a graph capture), else None"""
-    ent = _stem_masks.get(x.data_ptr())
-    if ent is None:
-        return None
-    if (ent[1] != tuple(x.shape) or ent[2] != x._version or ent[3]() is None
-            or ent[4] != torch.cuda.is_current_stream_capturing()):
-        return None
-    return ent[0]
-
-
-def stem_mask_forget(t):
-    """t (or a leading slice of it) is about to be overwritten by a kernel that takes a raw pointer - mmh_pack_nhwc* into the
-    static buffers of a captured iteration, into one half of a two-batch buffer: torch's version counter does not see that
-    write, so a mask cached for the old contents must go (an eager forward between two replays would otherwise skip what
-    the old batch did not have)"""
-    _stem_masks.pop(t.data_ptr(), None)
+# stem_mask_forget(t): t (or a leading slice of it) is about to be overwritten by a kernel that takes a raw pointer -
+# mmh_pack_nhwc* into the static buffers of a captured iteration, into one half of a two-batch buffer - which torch's version
+# counter does not see (an eager forward between two replays would otherwise skip what the old batch did not have)
+stem_mask_forget = _stem_masks.drop
 
 
 def stem_mask_request(x, cout=64):
@@ -564,14 +552,9 @@ def stem_mask_request(x, cout=64):
     mask = _stem_mask_for(x)
     if mask is not None:
         return mask
-    if len(_stem_masks) >= 8:
-        # only entries whose tensor is gone: a live one is still owed to its stem's wgrad (dropping it would send that
-        # wgrad to the dense kernel, five times as long, depending on what else happened to be cached)
-        for k in [k for k, e in _stem_masks.items() if e[3]() is None]:
-            del _stem_masks[k]
     mask = torch.empty((nbytes // 8,), dtype=torch.int64, device=x.device)
     L.call("mmh_stem_activity", _ptr(x), B, H, W_, Cc, _ptr(mask), _stream())
-    _stem_masks[x.data_ptr()] = (mask, tuple(x.shape), x._version, weakref.ref(x), torch.cuda.is_current_stream_capturing())
+    _stem_masks.put(x, mask, keep=True)
     return mask
 
 
@@ -1205,18 +1188,7 @@ class NormBwdSite:
         self.g = self.s1 = self.s2 = None
 
 
-_nbr_sites = {}
-
-
-def nbr_site_put(a16, site):
-    while len(_nbr_sites) >= 8:         # bounded: sites whose consumer was not a conv of this kind
-        _nbr_sites.pop(next(iter(_nbr_sites)))
-    _nbr_sites[a16.data_ptr()] = (a16, site)
-
-
-def nbr_site_take(a16):
-    ent = _nbr_sites.pop(a16.data_ptr(), None)
-    return ent[1] if ent is not None and ent[0] is a16 else None
+nbr_site_put, nbr_site_take = _nbr_sites.put, _nbr_sites.get     # (a16, site) / (a16); bounded: the consumer may be no such conv
 
 
 def raw_conv3x3_lp16(x16, w, bias, reflect, act, bf16, mode, out16=False, want_stats=False, addend=None, nbr=None):
@@ -1338,35 +1310,25 @@ def flat8_weights(w, bf16):
 # fp32 NHWC tensor): raw_pack(twin=lp) parks the copy here under the fp32 tensor's address and version, lp16_pad8 takes it
 # instead of running mmh_lp16_pad_cvt over the tensor.  MMH_PACK_TWIN=0: off.
 USE_PACK_TWIN = os.environ.get("MMH_PACK_TWIN", "1") != "0"
-_pack_twins = {}
 
 
-def pack_twin_put(x, x16p, keep=False):
-    """x16p is what lp16_pad8(x) would return; x may be a zero-stride proxy (lp_proxy) that is never read.  keep: the entry
-    survives its use (a model input that several steps read; dropped by pack_twin_drop), else the first lp16_pad8 takes it."""
-    while len(_pack_twins) >= 16:       # bounded: entries of tensors that never reached a stem
-        _pack_twins.pop(next(iter(_pack_twins)))
-    # a DETACHED alias is held (same storage, same version counter): the address stays unique while the entry lives, and an
-    # entry no stem consumes does not pin the autograd graph of the PackFn output it was parked under (ADVICE r5)
-    _pack_twins[x.data_ptr()] = (x.detach(), x._version, x16p, keep)
+# pack_twin_put(x, x16p, keep=False): x16p is what lp16_pad8(x) would return; x may be a zero-stride proxy (lp_proxy) that is
+# never read.  keep: the entry survives its use (a model input that several steps read; dropped by pack_twin_drop), else the
+# first lp16_pad8 takes it.  Held by a detached alias: an unconsumed entry does not pin the PackFn output's graph.
+pack_twin_put = _pack_twins.put
 
 
 def pack_twin_drop(x):
     if x is not None:
-        _pack_twins.pop(x.data_ptr(), None)
+        _pack_twins.drop(x)
 
 
 def pack_twin_get(x, bf16, pop=True):
-    ent = _pack_twins.get(x.data_ptr())
-    if ent is None:
+    x16p = _pack_twins.get(x, pop)
+    if x16p is not None and (x16p.dtype != _wd(bf16) or tuple(x16p.shape) != (*x.shape[:3], (x.shape[3] + 7) // 8 * 8)):
+        _pack_twins.drop(x)             # another operand type asked than the one parked
         return None
-    x0, ver, x16p, keep = ent
-    B, H, W_, Cc = x.shape
-    ok = ((x0 is x or (x0.shape == x.shape and x0.stride() == x.stride())) and x0._version == ver and x._version == ver
-          and x16p.dtype == _wd(bf16) and tuple(x16p.shape) == (B, H, W_, (Cc + 7) // 8 * 8))
-    if not ok or (pop and not keep):
-        del _pack_twins[x.data_ptr()]
-    return x16p if ok else None
+    return x16p
 
 
 def lp16_pad8(x, bf16, out=None):
@@ -1546,34 +1508,19 @@ def _tdt(t):
     return {torch.float32: L.F32, torch.bfloat16: L.BF16, torch.float16: L.FP16}[t.dtype]
 
 
-# Gradients of 16-bit edges.  autograd validates a gradient against the fp32 proxy on the edge, so the
-# producer of a 16-bit gradient returns a fresh proxy and parks the real tensor here under the proxy's
-# address; the consumer (the backward of the node on the other side of the edge) takes it out.  An edge
-# with two consumers would make autograd add the proxies - the lookup then fails loudly.
-_lp_grads = {}
-
-
+# Gradients of 16-bit edges.  autograd validates a gradient against the fp32 proxy on the edge, so the producer of a 16-bit
+# gradient returns a fresh proxy and leaves the real tensor under it (_lp_grads); the consumer (the backward of the node on the
+# other side of the edge) takes it out.  An edge with two consumers would make autograd add the proxies: the lookup fails loudly.
 def lp_grad_out(t16):
-    p = lp_proxy(t16.shape, t16.device)
-    _lp_grads[p.data_ptr()] = (p, t16)        # p is held so that its address stays unique
-    return p
+    return _lp_grads.put(lp_proxy(t16.shape, t16.device), t16)      # -> the proxy; held, so its address stays unique
 
 
 def lp_grad_in(g, what):
-    ent = _lp_grads.pop(g.data_ptr(), None) if g is not None else None
-    if ent is None or tuple(ent[1].shape) != tuple(g.shape):
+    t16 = _lp_grads.get(g) if g is not None else None
+    if t16 is None:
         raise RuntimeError(f"{what}: the gradient of a 16-bit edge did not arrive through the 16-bit channel "
                            "(an edge with more than one consumer, or a foreign backward node)")
-    return ent[1]
-
-
-def lp_grads_reset():
-    """drop gradients parked by a backward pass that did not finish"""
-    _lp_grads.clear()
-    _nb_defer.clear()
-    _nbr_sites.clear()
-    for k in [k for k, ent in _pack_twins.items() if not ent[3]]:      # kept entries belong to model inputs (pack_twin_drop)
-        del _pack_twins[k]
+    return t16
 
 
 # Norm-apply fused into the neighbouring convolutions (fp32, Winograd F(6x6,3x3) stack; models/Generator.py:66-77
@@ -1600,20 +1547,15 @@ class NormBwdDefer:
                  "rows", "relu", "drop_p")
 
 
-_nb_defer = {}
-
-
 def norm_bwd_defer_out(ent):
-    p = lp_proxy(ent.x.shape, ent.x.device)
-    _nb_defer[p.data_ptr()] = (p, ent)
-    return p
+    return _nb_defer.put(lp_proxy(ent.x.shape, ent.x.device), ent)
 
 
 def norm_bwd_defer_in(g, what):
-    ent = _nb_defer.pop(g.data_ptr(), None) if g is not None else None
-    if ent is None or tuple(ent[1].x.shape) != tuple(g.shape):
+    ent = _nb_defer.get(g) if g is not None else None
+    if ent is None:
         raise RuntimeError(f"{what}: expected the deferred gradient of a fused norm (NormBwdDefer) on this edge")
-    return ent[1]
+    return ent
 
 
 def raw_norm_bwd_apply_rc(e):

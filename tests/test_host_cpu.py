@@ -533,7 +533,7 @@ def test_pack_twin_and_norm_site_registries_hand_over_once_and_notice_stale_tens
     for h in held[:20]:
         ops.nbr_site_put(h, site)
     assert len(ops._nbr_sites) <= 8
-    ops.lp_grads_reset()
+    ops.handover_reset()
     assert not ops._nbr_sites
     ops._pack_twins.clear()
 

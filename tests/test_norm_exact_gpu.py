@@ -507,10 +507,9 @@ def test_epilogue_statistics_partials_exact(kind, lp, dev, monkeypatch):
         y = ops.raw_conv_lp16_flat(d, x, w, bias, 0, LPARG[lp], out16=True, want_stats=True)
         entry = "mmh_conv_stem16_stats"
     assert calls.get(entry) == 1, calls
-    pend = ops._pending_stats.get(y.data_ptr())
+    pend = ops._take_stats(y)                   # this test's own entry, nothing else
     assert pend is not None, "the kernel left no partial statistics"
     stats = pend[0].double().cpu()
-    ops._pending_stats.pop(y.data_ptr())        # this test's own entry, nothing else
     E.assert_exact(y, P.y, f"{entry} y")
     assert stats.shape[0] == B and stats.shape[2] == 3 and stats.shape[3] == Cout and bool(torch.isfinite(stats).all())
     n, mean, m2 = stats[:, :, 0], stats[:, :, 1], stats[:, :, 2]

@@ -218,7 +218,7 @@ def test_stats_merge_and_finalize_in_one_launch(dev):
     x = _mk((2, 20, 16, 128), 1, dev)
     w = _mk((3, 3, 128, 128), 2, dev, 0.05)
     y = ops.raw_conv_fprop_wino(x, w, None, True, 0, 6)
-    stats = ops._pending_stats[y.data_ptr()][0].clone()
+    stats = ops._take_stats(y, peek=True)[0].clone()
     B, H, W, C = y.shape
     fast = ops.raw_norm_stats_finalize_pending(y, B)
     assert fast is not None and not ops._pending_stats
@@ -252,7 +252,6 @@ def test_direct_fprop_leaves_output_statistics(Cin, Cout, k, stride, pad, reflec
     y_plain = ops.raw_conv_fprop(x, w, bias, stride, pad, reflect)
     assert torch.equal(y, y_plain)
     ops._pending_stats.clear()
-    ops._pending_stats[y.data_ptr()] = None      # placeholder, replaced below
     y2 = ops.raw_conv_fprop(x, w, bias, stride, pad, reflect, want_stats=True)
     fast = ops.raw_norm_stats_finalize_pending(y2, B)
     assert fast is not None
@@ -268,3 +267,40 @@ def test_direct_fprop_leaves_output_statistics(Cin, Cout, k, stride, pad, reflec
         yy = ops.raw_conv_fprop(x, w, bias, stride, pad, reflect, want_stats=True)
         outs.append(ops.NormActFn.apply(yy, None, None, None, None, None, "instance", True, 0.0, 0, None, None))
     assert float((outs[0] - outs[1]).abs().max()) < 2e-5
+
+
+def _conv_with_stats(dev, monkeypatch):
+    """B=2, 16x16, 4 -> 64, k 3 with the statistics epilogue -> (y, the names of the entry points called from now on)"""
+    from mmhand_amd import lib as L, ops
+    ops._pending_stats.clear()
+    y = ops.raw_conv_fprop(_mk((2, 16, 16, 4), 1, dev), _mk((3, 3, 4, 64), 2, dev, 0.05), _mk((64,), 3, dev), 1, 1, False,
+                           want_stats=True)
+    assert y.data_ptr() in ops._pending_stats
+    calls, real = [], L.call
+    monkeypatch.setattr(L, "call", lambda n, *a: (calls.append(n), real(n, *a))[1])
+    return y, calls
+
+
+def test_live_statistics_are_merged_once(dev, monkeypatch):
+    from mmhand_amd import ops
+    y, calls = _conv_with_stats(dev, monkeypatch)
+    ops.raw_norm_stats(y, 2)
+    assert "mmh_norm_stats_merge" in calls and "mmh_norm_stats" not in calls, calls
+    del calls[:]
+    ops.raw_norm_stats(y, 2)            # the entry was consumed
+    assert calls == ["mmh_norm_stats"]
+
+
+def test_statistics_of_a_dead_conv_output_are_not_taken(dev, monkeypatch):
+    """a new tensor at the dead output's address, with its shape, strides and version: only the dead anchor tells them apart"""
+    from mmhand_amd import ops
+    y, calls = _conv_with_stats(dev, monkeypatch)
+    st, ptr, shape, stride, version = y.untyped_storage(), y.data_ptr(), y.shape, y.stride(), y._version
+    del y
+    z = torch.empty(0, device=dev).set_(st, 0, shape).data          # .data: a version counter of its own, at 0
+    while z._version < version:
+        z.mul_(1)
+    assert (z.data_ptr(), z.shape, z.stride(), z._version) == (ptr, shape, stride, version) and ptr in ops._pending_stats
+    ops.raw_norm_stats(z, 2)
+    assert "mmh_norm_stats" in calls and "mmh_norm_stats_merge" not in calls, calls
+    assert not ops._pending_stats

@@ -172,6 +172,41 @@ def test_sparse_wgrad_is_the_dense_stem_wgrad_bit_for_bit(dev):
         assert torch.equal(routed, _wgrad(x, dy, False)), C
 
 
+def test_cached_mask_serves_only_the_tensor_and_contents_it_was_made_from(dev, monkeypatch):
+    """ops.stem_mask_request computes once per tensor; an in-place write, stem_mask_forget, a new tensor at a dead one's
+    address (same shape, strides and version) and the other side of a graph capture each make a new mask pass"""
+    from mmhand_amd import lib as L, ops
+    calls, real = [], L.call
+    monkeypatch.setattr(L, "call", lambda n, *a: (calls.append(n), real(n, *a))[1])
+    ops._stem_masks.clear()
+    x = _pose_input(24, dev, 11)
+    masks = [ops.stem_mask_request(x)]
+
+    def again(t, launches):
+        masks.append(ops.stem_mask_request(t))
+        assert calls.count("mmh_stem_activity") == launches
+        assert masks[-1] is not None and torch.equal(masks[-1], masks[0])
+        return masks[-1]
+    assert masks[0] is not None and calls.count("mmh_stem_activity") == 1
+    assert again(x, 1) is masks[0]
+    x.mul_(1)
+    assert again(x, 2) is not masks[0]
+    ops.stem_mask_forget(x)
+    assert again(x, 3) is not masks[-2]
+    st, ptr, shape, stride, version = x.untyped_storage(), x.data_ptr(), x.shape, x.stride(), x._version
+    del x
+    z = torch.empty(0, device=dev).set_(st, 0, shape).data          # .data: a version counter of its own, at 0
+    while z._version < version:
+        z.mul_(1)
+    assert (z.data_ptr(), z.shape, z.stride(), z._version) == (ptr, shape, stride, version) and ptr in ops._stem_masks
+    assert again(z, 4) is not masks[-2]
+    assert again(z, 4) is masks[-2]
+    monkeypatch.setattr(torch.cuda, "is_current_stream_capturing", lambda: True)
+    assert again(z, 5) is not masks[-2]         # made eagerly: not for a capture
+    monkeypatch.undo()
+    ops._stem_masks.clear()
+
+
 def _dw_oracle(x, dy):
     C = x.shape[3]
     return R.conv2d_grads(x.cpu(), torch.zeros((7, 7, C, 64)), None, dy.cpu(), 1, 3, True)[2]
