@@ -1195,6 +1195,49 @@ size_t mmh_inception_score_ws_bytes(int n, int classes);
 int mmh_inception_score(const float* logits, int n, int cs, int classes, double* kl, double* py, void* ws, size_t ws_bytes,
                         mmh_stream_t s);
 
+/* ---- training the 2D hand-pose estimator (mmhand_amd/hpe_train.py; csrc/hpe_train.hip).  The reference has the network
+ *      (networks/net_hpm2d.py) and the target (data/RHD_dataset.py:245-277) and no training loop; the loss below - the sum
+ *      over the stage outputs of nn.MSELoss() against one Gaussian target - is this port's recipe.                          */
+
+/* replaces, for all S stage outputs at once (1 <= S <= 8; Hpm2d has 6): nn.Upsample(scale_factor=8, mode='bilinear',
+ * align_corners=True) (net_hpm2d.py:69,118), the target of RHD_dataset.py:245-277, nn.MSELoss() and its backward through the
+ * upsample.  No full-resolution tensor is written.
+ * heat: HOST array of S device pointers, each fp32 [B][h][w][cs], cs >= 21, joints in lanes 0..20.  uv: device float64
+ * [B][21][2] = (x, y) on the 8h x 8w grid.  weight: HOST array of S doubles.  loss: device float64 [S].  dheat: NULL (loss
+ * only) or a HOST array of S device pointers, each fp32 [B][h][w][dcs], dcs >= 24: lanes 0..20 receive the gradient, lanes
+ * 21..23 zeros, no other lane is touched.  Definition, N = B * 21 * 8h * 8w:
+ *   up   = the fp32 value mmh_heatmap_upsample_argmax defines (float64 taps, no fused multiply-add, one rounding);
+ *   t    = (float)clip(exp(-D2 / 2.0 / sigma / sigma)), D2 = (ox - x)^2 + (oy - y)^2 in float64 without fused multiply-add,
+ *          values above 1 -> 1, values below 0.0099 -> 0;  d = (double)up - (double)t;
+ *   loss[s] = sum d^2 / N in float64: per low-res pixel and joint over the outputs whose taps 0 are that pixel in ascending
+ *          (oy, ox) order, then a fixed tree over a workgroup's 8 pixels x 24 lanes, then the workgroups in a fixed order;
+ *   dheat[s][b,y,x,j] = (float) sum over (oy, ox) ascending of (ay * ax) * ((2 weight[s] / N) * d), float64, where ay / ax
+ *          is the bilinear weight with which output row oy / column ox reads source row y / column x (both taps added
+ *          where they are the same row / column).
+ * Gather form, no atomics: bit-identical run to run.  The target of an output pixel is computed once per visit and shared by
+ * the S stages; exp is left out only where -D2 / 2 / sigma^2 < -5 (e^-5 = 0.0067, a third under the cut: the target is 0
+ * whatever exp returns).  ws: mmh_heatmap_mse_ws_bytes(S, B, h, w) bytes (0 = refused), 8-byte aligned like uv and loss.    */
+size_t mmh_heatmap_mse_ws_bytes(int S, int B, int h, int w);
+int mmh_heatmap_mse(const float* const* heat, int S, int B, int h, int w, int cs, const double* uv, double sigma,
+                    const double* weight, double* loss, float* const* dheat, int dcs, void* ws, size_t ws_bytes, mmh_stream_t s);
+
+/* The estimator's first convolution for training (networks/net_hpm2d.py:40,75: nn.Conv2d(3, 64, 3, padding=1) + ReLU) with
+ * float64 accumulation.  x: fp32 [B][H][W][4] (mmh_hpe_normalize's output, lane 3 zero); w: RSCK fp32 [3][3][4][Cout], Cout % 4
+ * == 0, Cout <= 256; y: fp32 [B][H][W] pixels of Cout lanes with pixel stride y_cs.  y = (float)(bias + sum x * w): every
+ * product of two fp32 values is exact in float64, the products of the taps inside the image are added to (double)bias in
+ * ascending (kh, kw, c) order without fused multiply-add, one rounding, then ReLU if act == MMH_ACT_RELU.  The sign of a
+ * pre-activation - the ReLU mask the backward reads - is therefore that of exact arithmetic down to 1e-16 of the terms: of all
+ * the layers this one's parameter gradients are summed over the fewest terms (27 inputs), and with the fp32 direct kernel one
+ * mask that fp32 rounding flips moved them by 4e-5.  Inference (hpe.Hpm2d) stays on mmh_conv2d_fprop; the two
+ * outputs differ by fp32 rounding.  x, w, bias and y 16-byte aligned.                                                        */
+int mmh_conv3x3_c4_fprop_f64(const float* x, const float* w, const float* bias, float* y, int B, int H, int W, int Cout, int y_cs,
+                             int act, mmh_stream_t s);
+
+/* y[p][c] += x[p][c] for `pixels` pixels and c < lanes (lanes % 4 == 0): x / y point at the first lane of the range inside
+ * NHWC buffers with pixel strides x_cs / y_cs (multiples of 4; 16-byte aligned pointers).  The backward of the reference's
+ * cat((heat, out_0), 1) (net_hpm2d.py:104-116): a stage's input gradient added onto the heat-map and out_0 gradients.       */
+int mmh_lane_add(const float* x, int x_cs, float* y, int y_cs, int64_t pixels, int lanes, mmh_stream_t s);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }

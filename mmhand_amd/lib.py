@@ -235,6 +235,10 @@ SIGNATURES = {
     "mmh_global_avgpool": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "mmh_inception_score_ws_bytes": (_sz, [_i, _i]),
     "mmh_inception_score": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "mmh_heatmap_mse_ws_bytes": (_sz, [_i, _i, _i, _i]),
+    "mmh_heatmap_mse": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _d, _vp, _vp, _vp, _i, _vp, _sz, _vp]),
+    "mmh_lane_add": (_i, [_vp, _i, _vp, _i, _i64, _i, _vp]),
+    "mmh_conv3x3_c4_fprop_f64": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
 }
 
 _lib = None
