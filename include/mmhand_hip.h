@@ -81,6 +81,9 @@ int mmh_version(void);
  * Every key (mmh_option_key enumerates the same list):
  *   fp32 implicit GEMM   "conv_dbuf" "conv_cw" "conv_bn256" "conv_levels" (1 | 2) "conv_xcd" "conv_xcd1" "conv_tall"
  *                        "dgrad_s2_multi" "dgrad_s2_halo" "border_bn64" "stem_f32"
+ *                        "dgrad_levels" (1 | 2; 2: mmh_conv2d_dgrad's fp32 implicit GEMM with more than 64 input channels sums
+ *                        every 32 of the (tap, channel) index in a chain of its own and adds the chains, as "conv_levels" 2
+ *                        does for the forward; the 3D estimator's trainer sets it for its backward and puts it back)
  *   sparse fp32 stems    "stem_sparse" (1: the mmh_conv7_stem_sparse_*_supported queries may say yes, 0: they say no and
  *                        every caller stays on the dense kernels - the forward is bit-identical either way)
  *                        "stem_sparse_flat" (0: only mmh_conv7_stem_sparse_wgrad_flat_supported says no)
@@ -1196,8 +1199,10 @@ int mmh_inception_score(const float* logits, int n, int cs, int classes, double*
                         mmh_stream_t s);
 
 /* ---- training the 2D hand-pose estimator (mmhand_amd/hpe_train.py; csrc/hpe_train.hip).  The reference has the network
- *      (networks/net_hpm2d.py) and the target (data/RHD_dataset.py:245-277) and no training loop; the loss below - the sum
- *      over the stage outputs of nn.MSELoss() against one Gaussian target - is this port's recipe.                          */
+ *      (networks/net_hpm2d.py), the target (data/RHD_dataset.py:245-277) and, under hand_pose_estimators/CVPR2020_hpm3d/models/,
+ *      its own training loops (hpm2d_model.py, hpm3d_model.py, hpm_model.py); hpm2d_model.py:143-151 is the loss below - the sum
+ *      over the stage outputs of nn.MSELoss() against one Gaussian target - with every weight 1000.  The weights' default of 1
+ *      is this port's.                                                                                                       */
 
 /* replaces, for all S stage outputs at once (1 <= S <= 8; Hpm2d has 6): nn.Upsample(scale_factor=8, mode='bilinear',
  * align_corners=True) (net_hpm2d.py:69,118), the target of RHD_dataset.py:245-277, nn.MSELoss() and its backward through the
@@ -1237,6 +1242,39 @@ int mmh_conv3x3_c4_fprop_f64(const float* x, const float* w, const float* bias, 
  * NHWC buffers with pixel strides x_cs / y_cs (multiples of 4; 16-byte aligned pointers).  The backward of the reference's
  * cat((heat, out_0), 1) (net_hpm2d.py:104-116): a stage's input gradient added onto the heat-map and out_0 gradients.       */
 int mmh_lane_add(const float* x, int x_cs, float* y, int y_cs, int64_t pixels, int lanes, mmh_stream_t s);
+
+/* ---- training the 3D hand-pose estimator (mmhand_amd/hpe_train.py: Hpm3dTrainer; csrc/hpe3d_train.hip).  The recipe is the
+ *      reference's: hand_pose_estimators/CVPR2020_hpm3d/models/hpm3d_model.py:73,91-113 trains Hpm3d(21, 21) on the ground-truth
+ *      heat maps against the labels' depth with nn.SmoothL1Loss() * 10 and Adam.  No atomics in any of the four; every output
+ *      element is written once, by one thread, with 16-byte stores where the rows are 16-byte aligned; the results do not
+ *      depend on the grid and are bit-identical run to run.                                                                */
+
+/* replaces RHD_dataset.py:129-137,192-200,245-277 (gen_heatmap of the 21 joints at full resolution: the input of Hpm3d) and
+ * the upload of that tensor.  uv: device float64 [B][21][2] = (x, y) in pixels of the H x W grid.  out: fp32 [B][H][W] pixels
+ * of cs lanes (cs >= 24, cs % 4 == 0): lanes 0..20 = t, the target mmh_heatmap_mse defines (one __device__ function serves
+ * both: csrc/hpe_target.h) - (float)clip(exp(-D2 / 2.0 / sigma / sigma)), D2 in float64 without fused multiply-add, values
+ * above 1 -> 1, values below 0.0099 -> 0, exp left out only where the exponent is below -5 -; lanes 21..23 zeros; no lane
+ * >= 24 is touched.  uv 8-byte, out 16-byte aligned.                                                                       */
+int mmh_gauss_heatmaps(const double* uv, int B, int H, int W, double sigma, float* out, int cs, mmh_stream_t s);
+
+/* replaces hpm3d_model.py:73,105 (torch.nn.SmoothL1Loss()(output, depth) * 10) and its backward.  pred: fp32 [M][ps], columns
+ * 0..n-1 read; target: device float64 [M][n]; M <= 64, n <= 24 <= dcs.  In float64, no fused multiply-add, d = (double)pred -
+ * target:  l = |d| < beta ? 0.5 * d * d / beta : |d| - 0.5 * beta  (torch's rule: at |d| == beta the linear branch);
+ *   loss[0] = scale * (sum of l in ascending (m, j) order) / (M n);
+ *   dpred[m][j] = (float)((scale / (M n)) * (|d| < beta ? d / beta : sign(d))), columns n..23 zeros, no column >= 24 touched.
+ * dpred NULL: the loss only.  One workgroup.  loss, target 8-byte, dpred 16-byte aligned; dcs % 4 == 0.                    */
+int mmh_smooth_l1(const float* pred, int ps, const double* target, int M, int n, double beta, double scale, double* loss,
+                  float* dpred, int dcs, mmh_stream_t s);
+
+/* replaces the backward of net_hpm3d.py:60-62,112-114 (nn.Linear) with respect to its input: dx [M][K], dx[m][k] = sum_n
+ * dy[m][n] * wt[k][n], wt in mmh_linear_fprop's layout [K][N]; one fp32 fma chain per element over n ascending from +0.
+ * M <= 64, N % 4 == 0.  dy, wt and dx 16-byte aligned.                                                                     */
+int mmh_linear_dgrad(const float* dy, const float* wt, float* dx, int M, int K, int N, mmh_stream_t s);
+
+/* replaces the backward of net_hpm3d.py:60-62,112-114 (nn.Linear) with respect to its parameters: dwt [K][N], dwt[k][n] =
+ * sum_m x[m][k] * dy[m][n], one fp32 fma chain over m ascending from +0, every element written; db [N] (may be NULL), db[n] =
+ * sum_m dy[m][n], plain fp32 adds over m ascending from +0.  M <= 64, N % 4 == 0.  dy, dwt and db 16-byte aligned.          */
+int mmh_linear_wgrad(const float* x, const float* dy, float* dwt, float* db, int M, int K, int N, mmh_stream_t s);
 
 #pragma GCC visibility pop
 #ifdef __cplusplus

@@ -218,7 +218,8 @@ __device__ __forceinline__ unsigned gather_off(const Gather& g, unsigned img_bas
 // barrier per k-step (2 workgroups/CU) instead of one buffer and two barriers
 // (3 workgroups/CU; measured 5-6 % faster on the 512-channel shapes).
 // ---------------------------------------------------------------------------
-// LEVELS = 2 (fprop form only; mmh_set_option("conv_levels", 2)): two-level summation over the contraction, as in
+// LEVELS = 2 (the fprop form under mmh_set_option("conv_levels", 2), the stride-1 dgrad form under "dgrad_levels" 2): two-level
+// summation over the contraction, as in
 // wino_gemm_kernel below - every k-step (32 of the (tap, channel) index) starts a fresh MFMA chain (C operand = 0) that is
 // folded into the totals by vector adds, one tile row at a time.  A k-ordered fp32 chain over K = 9 * 512 carries a relative
 // rounding error of ~u sqrt(K) / 2.4 = 1.1e-6 (oneDNN's blocked accumulation on the CPU: 2.4e-7), and at 256x256 the
@@ -234,7 +235,7 @@ __device__ __forceinline__ void conv_igemm_body(const ConvKP& p, const int bx, c
     static_assert(WAVES_M * WAVES_N == 4, "4 waves");
 
     constexpr int NBUF = DBUF ? 2 : 1;
-    constexpr bool IL = B_NMAJOR;   // dgrad: loads interleaved with the MFMA groups (+1-2 % measured)
+    constexpr bool IL = B_NMAJOR && LEVELS == 1;   // dgrad: loads interleaved with the MFMA groups (+1-2 % measured)
     constexpr int ASZ = BMT * LDA;
     constexpr int BSZ = B_NMAJOR ? BN * LDA : BK * BN;
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -453,7 +454,7 @@ __device__ __forceinline__ void conv_igemm_body(const ConvKP& p, const int bx, c
             if (!(p.dbg & 4)) kstate_next(ks_t, g);        // dbg 4: loads still issue, from stale addresses
             if (!(p.dbg & 1) && !IL) load_tiles(ks + 1);   // global -> registers, one burst
         }
-        if constexpr (LEVELS == 2 && !B_NMAJOR) {
+        if constexpr (LEVELS == 2) {
 #pragma unroll
             for (int i = 0; i < TM; ++i) {
                 f32x16 part[TN];
@@ -461,10 +462,18 @@ __device__ __forceinline__ void conv_igemm_body(const ConvKP& p, const int bx, c
                 for (int kg = 0; kg < 4; ++kg) {
                     const float4 av = *reinterpret_cast<const float4*>(&As[(wm * WTM + i * 32 + l31) * LDA + kg * 8 + h * 4]);
                     float bsc[TN][4];
+                    if constexpr (B_NMAJOR) {
 #pragma unroll
-                    for (int j = 0; j < TN; ++j)
+                        for (int j = 0; j < TN; ++j) {
+                            const float4 t = *reinterpret_cast<const float4*>(&Bs[(wn * WTN + j * 32 + l31) * LDA + kg * 8 + h * 4]);
+                            bsc[j][0] = t.x; bsc[j][1] = t.y; bsc[j][2] = t.z; bsc[j][3] = t.w;
+                        }
+                    } else {
 #pragma unroll
-                        for (int e = 0; e < 4; ++e) bsc[j][e] = Bs[(kg * 8 + h * 4 + e) * BN + wn * WTN + j * 32 + l31];
+                        for (int j = 0; j < TN; ++j)
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) bsc[j][e] = Bs[(kg * 8 + h * 4 + e) * BN + wn * WTN + j * 32 + l31];
+                    }
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         const float a = e == 0 ? av.x : e == 1 ? av.y : e == 2 ? av.z : av.w;
@@ -601,6 +610,11 @@ __global__ void __launch_bounds__(256, 2) conv_igemm_kernel(const ConvKP p) {
 // the fprop form with two-level summation (LEVELS = 2 above): 128 x 128 block tile, wave tile 64 x 64
 __global__ void __launch_bounds__(256, 2) conv_igemm_levels2_kernel(const ConvKP p) {
     conv_igemm_body<128, 2, 2, false, false, 128, 2>(p, blockIdx.x, blockIdx.y, gridDim.x, gridDim.y);
+}
+
+// the dgrad form with two-level summation (mmh_set_option("dgrad_levels", 2)): the same tile, the weights n-major
+__global__ void __launch_bounds__(256, 2) conv_igemm_dgrad_levels2_kernel(const ConvKP p) {
+    conv_igemm_body<128, 2, 2, true, false, 128, 2>(p, blockIdx.x, blockIdx.y, gridDim.x, gridDim.y);
 }
 
 // 256-row tiles for the narrow GEMMs (N <= 64: 7x7 stems, stride-2 dgrad): per MFMA half the weight
@@ -2344,9 +2358,26 @@ int launch_conv_levels2(const ConvKP& p, hipStream_t st) {
     return mmh::check_launch("conv_igemm_levels2_kernel");
 }
 
+int g_dgrad_levels = 1; // 2: the stride-1 fp32 dgrad with more than 64 input channels on conv_igemm_dgrad_levels2_kernel
+
+int launch_dgrad_levels2(const ConvKP& p, hipStream_t st) {
+    constexpr size_t lds = (BM * LDA + 128 * LDA) * sizeof(float) + tab_bytes(BM);
+    static int ready = -1;
+    if (ready != 0) ready = allow_lds(conv_igemm_dgrad_levels2_kernel, lds);
+    if (ready != 0) return ready;
+    dim3 grid((p.N + 127) / 128, (p.M + BM - 1) / BM);
+    hipLaunchKernelGGL(conv_igemm_dgrad_levels2_kernel, grid, dim3(256), lds, st, p);
+    return mmh::check_launch("conv_igemm_dgrad_levels2_kernel");
+}
+
 template <bool NMAJOR>
 int launch_conv(const ConvKP& p, hipStream_t st) {
     const_cast<ConvKP&>(p).dbg = g_conv_dbg;
+    if (g_dgrad_levels == 2 && NMAJOR && p.N > 64 && !p.stats && !p.accum) {
+        const int gx = (p.N + 127) / 128, gy = (p.M + BM - 1) / BM;
+        const_cast<ConvKP&>(p).xcd_remap = (g_conv_xcd && gx > 1 && gy >= 8) ? 1 : 0;
+        return launch_dgrad_levels2(p, st);
+    }
     if (g_conv_levels == 2 && !NMAJOR && p.N > 64 && p.g.chunk_major) {
         const int gx = (p.N + 127) / 128, gy = (p.M + BM - 1) / BM;
         const_cast<ConvKP&>(p).xcd_remap = (g_conv_xcd && gx > 1 && gy >= 8) ? 1 : 0;
@@ -3192,6 +3223,7 @@ const OptionEntry* option_table(int* count) {
         {"conv_cw", &g_conv_cw},
         {"conv_bn256", &g_conv_bn256},
         {"conv_levels", &g_conv_levels},
+        {"dgrad_levels", &g_dgrad_levels},
         {"wino_bn256", &g_wino_bn256},
         {"conv_xcd", &g_conv_xcd},
         {"conv_xcd1", &g_conv_xcd1},
@@ -3261,6 +3293,7 @@ int mmh_set_option(const char* key, int value) {
     const OptionEntry* e = find_option(key);
     if (!e) return mmh::fail("mmh_set_option: unknown key '%s'", key);
     if (e->value == &g_conv_levels) { g_conv_levels = value == 2 ? 2 : 1; mmh::g_stem_f32_levels = g_conv_levels; return 0; }
+    if (e->value == &g_dgrad_levels) { g_dgrad_levels = value == 2 ? 2 : 1; return 0; }
     if (e->value == &mmh::g_col_chunks || e->value == &mmh::g_row_chunks)
         MMH_REQUIRE(value > 0, "mmh_set_option: '%s' needs a value > 0, got %d", key, value);
     *e->value = value;

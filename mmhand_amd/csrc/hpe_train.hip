@@ -10,6 +10,7 @@
 //     gradient of the cat buffer's lanes onto a dense buffer).
 #include <cmath>
 #include "common.h"
+#include "hpe_target.h"
 
 namespace {
 
@@ -20,10 +21,6 @@ constexpr int HM_PX = 8;         // low-res pixels per workgroup
 constexpr int HM_TPB = HM_PX * HM_C;   // 192: three waves
 constexpr int HM_SMAX = 8;
 constexpr int HM_FIN_TPB = 64;
-
-// exp(-q) is below e^-5 = 0.0067 for q > 5: a third under the cut at 0.0099, against an error of the float64 exp near 1e-16.
-// Such a target is 0 whatever exp would have returned, so leaving the call out cannot change a bit.
-constexpr double HM_SKIP_Q = 5.0;
 
 struct HmArgs {
     const float* heat[HM_SMAX];
@@ -55,22 +52,10 @@ __device__ __forceinline__ int first_out(int i, int n_src, int n_out) {
     return o;
 }
 
-__device__ __forceinline__ float hm_target(double ox, double oy, double ux, double uy, double sigma) {
-#pragma clang fp contract(off)
-    const double dx = ox - ux, dy = oy - uy;
-    const double d2 = dx * dx + dy * dy;
-    const double q = d2 / 2.0 / sigma / sigma;
-    if (q > HM_SKIP_Q) return 0.f;
-    double v = exp(-q);
-    if (v > 1.0) v = 1.0;
-    if (v < 0.0099) v = 0.0;
-    return (float)v;
-}
-
 // one quadrant of a thread's window: the outputs whose row tap QY and column tap QX are (y, x)
 template <int S, int QY, int QX>
 __device__ __forceinline__ void hm_quadrant(const HmArgs& a, int64_t img, int h, int w, int cs, int y, int x, int c, double ux,
-                                            double uy, double sigma, double (&g)[S], double (&sq)[S]) {
+                                            double uy, double sigma, double far2, double (&g)[S], double (&sq)[S]) {
 #pragma clang fp contract(off)
     const int Ho = h * UP, Wo = w * UP;
     const int r0 = y - 1 + QY, c0 = x - 1 + QX;          // tap 0 of this quadrant's outputs
@@ -95,7 +80,7 @@ __device__ __forceinline__ void hm_quadrant(const HmArgs& a, int64_t img, int h,
         for (int ox = ox_lo; ox < ox_hi; ++ox) {
             const UpTap tx = up_tap(ox, w, Wo);
             const double ax = QX == 0 ? tx.w : (tx.i1 == x ? (1.0 - tx.w) + tx.w : 1.0 - tx.w);
-            const double t = (double)hm_target((double)ox, (double)oy, ux, uy, sigma);
+            const double t = (double)mmh::hm_target((double)ox, (double)oy, ux, uy, sigma, far2);
             const double aw = ay * ax;
 #pragma unroll
             for (int s = 0; s < S; ++s) {
@@ -124,10 +109,11 @@ __global__ void __launch_bounds__(HM_TPB) heatmap_mse_kernel(HmArgs a, int h, in
     if (live) {
         const int y = p / w, x = p % w;
         const double ux = uv[((int64_t)b * HM_J + c) * 2], uy = uv[((int64_t)b * HM_J + c) * 2 + 1];
-        hm_quadrant<S, 0, 0>(a, b, h, w, cs, y, x, c, ux, uy, sigma, g, sq);
-        hm_quadrant<S, 0, 1>(a, b, h, w, cs, y, x, c, ux, uy, sigma, g, sq);
-        hm_quadrant<S, 1, 0>(a, b, h, w, cs, y, x, c, ux, uy, sigma, g, sq);
-        hm_quadrant<S, 1, 1>(a, b, h, w, cs, y, x, c, ux, uy, sigma, g, sq);
+        const double far2 = mmh::hm_far2(sigma);
+        hm_quadrant<S, 0, 0>(a, b, h, w, cs, y, x, c, ux, uy, sigma, far2, g, sq);
+        hm_quadrant<S, 0, 1>(a, b, h, w, cs, y, x, c, ux, uy, sigma, far2, g, sq);
+        hm_quadrant<S, 1, 0>(a, b, h, w, cs, y, x, c, ux, uy, sigma, far2, g, sq);
+        hm_quadrant<S, 1, 1>(a, b, h, w, cs, y, x, c, ux, uy, sigma, far2, g, sq);
     }
     if (write_grad && p < h * w) {
 #pragma unroll

@@ -239,6 +239,10 @@ SIGNATURES = {
     "mmh_heatmap_mse": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _d, _vp, _vp, _vp, _i, _vp, _sz, _vp]),
     "mmh_lane_add": (_i, [_vp, _i, _vp, _i, _i64, _i, _vp]),
     "mmh_conv3x3_c4_fprop_f64": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "mmh_gauss_heatmaps": (_i, [_vp, _i, _i, _i, _d, _vp, _i, _vp]),
+    "mmh_smooth_l1": (_i, [_vp, _i, _vp, _i, _i, _d, _d, _vp, _vp, _i, _vp]),
+    "mmh_linear_dgrad": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
+    "mmh_linear_wgrad": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
 }
 
 _lib = None

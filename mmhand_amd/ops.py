@@ -18,6 +18,7 @@ import math
 import os
 import weakref
 
+import numpy as np
 import torch
 
 from . import lib as L
@@ -3551,6 +3552,71 @@ def linear(x, wt, bias=None, splits=0):
     y = _empty((M, N), x)
     L.call("mmh_linear_fprop", _ptr(x), _ptr(wt), _ptr(bias), _ptr(y), M, K, N, int(splits), _ptr(ws), nbytes, _stream())
     return y
+
+
+# ----------------------------------------------------------------------------- the 3D estimator's training (csrc/hpe3d_train.hip)
+def _uv64(uv, device):
+    if not torch.is_tensor(uv):
+        uv = torch.from_numpy(np.asarray(uv, dtype=np.float64))
+    return uv.to(device, torch.float64).reshape(-1, 21, 2).contiguous()
+
+
+def gauss_heatmaps(uv, H, W_, sigma=5.0, out=None, device=None):
+    """the 21 Gaussian maps of RHD_dataset.py:245-277 at H x W_: uv float64 [B,21,2] (host or device) -> fp32 [B,H,W_,24], lanes
+    21..23 zero; out: an fp32 [B,H,W_,cs >= 24] buffer whose lanes 0..23 are written instead.  The values are mmh_heatmap_mse's
+    target, bit for bit."""
+    uv = _uv64(uv, out.device if out is not None else (device if device is not None else uv.device))
+    B = uv.shape[0]
+    if out is None:
+        out = torch.empty((B, H, W_, 24), dtype=torch.float32, device=uv.device)
+    _chk(out, "out")
+    if out.dim() != 4 or tuple(out.shape[:3]) != (B, H, W_) or not uv.is_cuda:
+        raise ValueError(f"gauss_heatmaps: out {tuple(out.shape)} for uv {tuple(uv.shape)} at {H} x {W_}")
+    L.call("mmh_gauss_heatmaps", _ptr(uv), B, H, W_, float(sigma), _ptr(out), out.shape[3], _stream())
+    return out
+
+
+def smooth_l1(pred, target, n=21, beta=1.0, scale=1.0, with_grad=True):
+    """nn.SmoothL1Loss()(pred[:, :n], target) * scale (hpm3d_model.py:73,105) in float64 -> (loss float64 [1] on the device,
+    dpred fp32 [M,24] with columns n.. zero, or None).  pred fp32 [M,ps >= n]; target [M,n], any real dtype, host or device."""
+    _chk(pred, "pred")
+    if not torch.is_tensor(target):
+        target = torch.from_numpy(np.asarray(target, dtype=np.float64))
+    M, ps = pred.shape
+    target = target.to(pred.device, torch.float64).reshape(M, n).contiguous()
+    loss = torch.empty(1, dtype=torch.float64, device=pred.device)
+    dpred = _empty((M, 24), pred) if with_grad else None
+    L.call("mmh_smooth_l1", _ptr(pred), ps, _ptr(target), M, int(n), float(beta), float(scale), _ptr(loss), _ptr(dpred), 24,
+           _stream())
+    return loss, dpred
+
+
+def linear_dgrad(dy, wt):
+    """dx [M,K] = dy [M,N] @ wt [K,N].t(): nn.Linear's input gradient with wt in ops.linear's layout; fp32, M <= 64, N % 4 == 0"""
+    _chk(dy, "dy"); _chk(wt, "wt")
+    if dy.dim() != 2 or wt.dim() != 2 or dy.shape[1] != wt.shape[1]:
+        raise ValueError(f"linear_dgrad: dy {tuple(dy.shape)}, wt {tuple(wt.shape)}")
+    M, N = dy.shape
+    dx = _empty((M, wt.shape[0]), dy)
+    L.call("mmh_linear_dgrad", _ptr(dy), _ptr(wt), _ptr(dx), M, wt.shape[0], N, _stream())
+    return dx
+
+
+def linear_wgrad(x, dy, dwt=None, db=None, with_bias=True):
+    """(dwt [K,N] = x [M,K].t() @ dy [M,N], db [N] = dy.sum(0) or None): nn.Linear's parameter gradients in ops.linear's layout;
+    fp32, M <= 64, N % 4 == 0.  dwt / db: buffers to write (e.g. views of a flat gradient buffer)."""
+    _chk(x, "x"); _chk(dy, "dy")
+    if x.dim() != 2 or dy.dim() != 2 or x.shape[0] != dy.shape[0]:
+        raise ValueError(f"linear_wgrad: x {tuple(x.shape)}, dy {tuple(dy.shape)}")
+    M, K = x.shape
+    N = dy.shape[1]
+    dwt = _empty((K, N), x) if dwt is None else _chk(dwt, "dwt")
+    if db is None and with_bias:
+        db = _empty((N,), x)
+    if tuple(dwt.shape) != (K, N) or (db is not None and tuple(_chk(db, "db").shape) != (N,)):
+        raise ValueError(f"linear_wgrad: dwt {tuple(dwt.shape)} / db for K = {K}, N = {N}")
+    L.call("mmh_linear_wgrad", _ptr(x), _ptr(dy), _ptr(dwt), _ptr(db), M, K, N, _stream())
+    return dwt, db
 
 
 # ----------------------------------------------------------------------------- Inception score passes (csrc/inception.hip)
