@@ -1182,8 +1182,37 @@ int mmh_inception_preprocess(const mmh_image_src* src, int B, int H, int W, cons
  * MMH_POOL_AVG, output H x W, the window's values inside the image summed in row-major order in fp32 and the sum divided by 9
  * - count_include_pad - with a correctly rounded fp32 division).  x: fp32 NHWC, C lanes (C % 4 == 0) from pointer x with pixel
  * stride x_cs; y likewise with y_cs: a pointer into a wider concat buffer writes only its own C lanes.  x, y 16-byte aligned. */
-enum { MMH_POOL_MAX = 0, MMH_POOL_AVG = 1 };
+enum { MMH_POOL_MAX = 0, MMH_POOL_AVG = 1, MMH_POOL_AVG_VALID = 2, MMH_POOL_MAX_S1 = 3 };
 int mmh_pool3x3_fwd(const float* x, int B, int H, int W, int C, int x_cs, float* y, int y_cs, int mode, mmh_stream_t s);
+/* the two further modes are pytorch-fid's departures from torchvision's graph (mmhand_amd/fid.py, variant "fid"), both stride 1,
+ * padding 1, output H x W: MMH_POOL_AVG_VALID is MMH_POOL_AVG's sum divided by the number of window pixels inside the image
+ * (F.avg_pool2d(..., count_include_pad=False)), the quotient correctly rounded likewise; MMH_POOL_MAX_S1 is the maximum over
+ * those pixels (F.max_pool2d(x, kernel_size=3, stride=1, padding=1)).  Modes 0 and 1 and their bits are what they were. */
+
+/* ---- Frechet and Kernel Inception Distance (mmhand_amd/fid.py; csrc/fid.hip).  The reference has neither metric; the
+ *      definitions are pytorch-fid's (mu, np.cov(rowvar=False)) and torch-fidelity's KID (kernel (x.y / d + 1)^3).
+ *
+ * mmh_feature_moments: X fp32 [N][d] row-major (16-byte aligned, d % 4 == 0, N >= 2) -> mean float64 [d], cov float64 [d][d].
+ *   mean[j]: float64 sums of 128-row chunks in row order, the chunks added in order, divided once by N.  cov[i][j] =
+ *   sum_n c[n][i] c[n][j] / (N - 1) with c = (double)x - mean formed on load: one chain of ceil(N / 4) v_mfma_f64_16x16x4_f64
+ *   over the rows in ascending order from a zero accumulator, the same bits wherever the element's tile lies; only the 64 x 64
+ *   tiles on or above the diagonal are multiplied and each element is also stored at its mirror.  fp32 -> fp64 and the
+ *   products of converted values are exact: the accumulation is the only rounding.  No atomics, no split over N.
+ *   ws: mmh_feature_moments_ws_bytes(N, d) bytes (0 = the arguments are refused), 8-byte aligned.
+ * mmh_poly_mmd_sums: A fp32 [Na][d], B fp32 [Nb][d]; idxA int32 [S][Ma], idxB int32 [S][Mb] name rows of A and B (the caller
+ *   guarantees 0 <= index < Na, Nb).  With a_p = A[idxA[s][p]], b_q = B[idxB[s][q]] and k(x, y) = (t t) t, t = x.y / d + 1.0
+ *   (no contraction): out[s] = { sum_{p != q} k(a_p, a_q), sum_{p != q} k(b_p, b_q), sum_{p, q} k(a_p, b_q) }, p != q by
+ *   POSITION in the list.  Every dot product is one chain of d / 4 MFMAs in ascending feature order; the Gram tiles never reach
+ *   memory: a 64 x 64 tile's sum (lane, butterfly, wave order) goes to the workspace and a second kernel adds a subset's tiles
+ *   in an order fixed by (Ma, Mb); the symmetric blocks multiply the upper tiles only and double them.  The launch shape
+ *   follows from (S, Ma, Mb, d) alone, so a subset's three sums do not depend on S or on its slot, bit for bit.
+ *   ws: mmh_poly_mmd_sums_ws_bytes(S, Ma, Mb) bytes (0 = refused).
+ * Bad arguments (NULL, d % 4 != 0, N < 2, S, Ma, Mb < 1, misalignment) return non-zero before any launch.                   */
+size_t mmh_feature_moments_ws_bytes(int N, int d);
+int mmh_feature_moments(const float* X, int N, int d, double* mean /* [d] */, double* cov /* [d][d] */, void* ws, mmh_stream_t s);
+size_t mmh_poly_mmd_sums_ws_bytes(int S, int Ma, int Mb);
+int mmh_poly_mmd_sums(const float* A, const float* B, int d, const int32_t* idxA /* [S][Ma] */, const int32_t* idxB /* [S][Mb] */,
+                      int S, int Ma, int Mb, double* out /* [S][3] */, void* ws, mmh_stream_t s);
 
 /* replaces inception.py:168 (F.adaptive_avg_pool2d(x, (1, 1))): x fp32 [B][H][W] pixels of C lanes with pixel stride x_cs ->
  * y fp32 [B][C] = (float)(sum / (H W)), the sum taken in float64 over the pixels in order.  One thread per value, no atomics. */

@@ -5,7 +5,8 @@
 //     ImagingResample runs them: a horizontal pass over the source rows into uint8, then a vertical pass over that.  Both are
 //     integer: clip8(((1 << 21) + sum pixel * k) >> 22) with the host's 22-bit coefficients.  Only the columns and rows that the
 //     centre-crop window reads are produced.  The last two transforms are a [3][256] table lookup.
-//   * pool3x3: max (stride 2, no padding) and average (stride 1, zero padding 1, / 9) over NHWC lanes, into a concat buffer.
+//   * pool3x3: max (stride 2, no padding) and average (stride 1, zero padding 1, / 9) over NHWC lanes, into a concat buffer;
+//     for pytorch-fid's graph (mmhand_amd/fid.py) also the average over the in-image pixels only and a stride-1 padded max.
 //   * global_avgpool: the mean over an image's pixels, accumulated in float64 in pixel order.
 //   * inception_score: float64 row softmax of the logits, the mean row py, and per row sum pyx * log(pyx / py).
 #include <cmath>
@@ -94,7 +95,8 @@ int launch_preprocess(const mmh_image_src& src, int B, int H, int W, const int32
 
 // ------------------------------------------------------------------------------------------------- pools
 // thread = (image, output pixel, lane quad).  MAX: window rows 2 oy .. 2 oy + 2, all inside.  AVG: rows oy - 1 .. oy + 1, the
-// ones inside summed in row-major order, the sum divided by 9 whatever their number (count_include_pad).
+// ones inside summed in row-major order, the sum divided by 9 whatever their number (count_include_pad).  AVG_VALID: the same
+// sum divided by the number of pixels inside (count_include_pad=False).  MAX_S1: the maximum over AVG's window.
 template <int MODE>
 __global__ void __launch_bounds__(TPB) pool3x3_kernel(const float* __restrict__ x, int B, int H, int W, int C4, int x_cs,
                                                       int Ho, int Wo, float* __restrict__ y, int y_cs) {
@@ -107,6 +109,7 @@ __global__ void __launch_bounds__(TPB) pool3x3_kernel(const float* __restrict__ 
     const int h0 = MODE == MMH_POOL_MAX ? 2 * oy : oy - 1, w0 = MODE == MMH_POOL_MAX ? 2 * ox : ox - 1;
     float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
     bool first = true;
+    int inside = 0;
 #pragma unroll
     for (int dh = 0; dh < 3; ++dh) {
 #pragma unroll
@@ -114,10 +117,11 @@ __global__ void __launch_bounds__(TPB) pool3x3_kernel(const float* __restrict__ 
             const int h = h0 + dh, w = w0 + dw;
             if (h < 0 || h >= H || w < 0 || w >= W) continue;
             const float4 v = *reinterpret_cast<const float4*>(x + (((int64_t)b * H + h) * W + w) * x_cs + q * 4);
+            ++inside;
             if (first) {
                 r = v;
                 first = false;
-            } else if (MODE == MMH_POOL_MAX) {
+            } else if (MODE == MMH_POOL_MAX || MODE == MMH_POOL_MAX_S1) {
                 r.x = v.x > r.x ? v.x : r.x; r.y = v.y > r.y ? v.y : r.y; r.z = v.z > r.z ? v.z : r.z; r.w = v.w > r.w ? v.w : r.w;
             } else {
                 r.x += v.x; r.y += v.y; r.z += v.z; r.w += v.w;
@@ -129,6 +133,11 @@ __global__ void __launch_bounds__(TPB) pool3x3_kernel(const float* __restrict__ 
         // fp32 division is
         r.x = (float)((double)r.x / 9.0); r.y = (float)((double)r.y / 9.0);
         r.z = (float)((double)r.z / 9.0); r.w = (float)((double)r.w / 9.0);
+    }
+    if (MODE == MMH_POOL_AVG_VALID) {       // 1 .. 9 pixels: the same correctly rounded quotient
+        const double n = (double)inside;
+        r.x = (float)((double)r.x / n); r.y = (float)((double)r.y / n);
+        r.z = (float)((double)r.z / n); r.w = (float)((double)r.w / n);
     }
     *reinterpret_cast<float4*>(y + px * y_cs + q * 4) = r;
 }
@@ -245,9 +254,10 @@ int mmh_inception_preprocess(const mmh_image_src* src, int B, int H, int W, cons
 
 int mmh_pool3x3_fwd(const float* x, int B, int H, int W, int C, int x_cs, float* y, int y_cs, int mode, mmh_stream_t s) {
     MMH_REQUIRE(x && y, "mmh_pool3x3_fwd: NULL buffer");
-    MMH_REQUIRE(mode == MMH_POOL_MAX || mode == MMH_POOL_AVG, "mmh_pool3x3_fwd: mode %d (MMH_POOL_MAX | MMH_POOL_AVG)", mode);
+    MMH_REQUIRE(mode == MMH_POOL_MAX || mode == MMH_POOL_AVG || mode == MMH_POOL_AVG_VALID || mode == MMH_POOL_MAX_S1,
+                "mmh_pool3x3_fwd: mode %d (MMH_POOL_MAX | MMH_POOL_AVG | MMH_POOL_AVG_VALID | MMH_POOL_MAX_S1)", mode);
     MMH_REQUIRE(B >= 1 && H >= 1 && W >= 1 && C >= 4 && C % 4 == 0 && x_cs % 4 == 0 && y_cs % 4 == 0 && x_cs >= C && y_cs >= C &&
-                    (mode == MMH_POOL_AVG || (H >= 3 && W >= 3)),
+                    (mode != MMH_POOL_MAX || (H >= 3 && W >= 3)),
                 "mmh_pool3x3_fwd: bad shape B=%d H=%d W=%d C=%d x_cs=%d y_cs=%d (lanes in fours; max needs H, W >= 3)", B, H, W, C,
                 x_cs, y_cs);
     MMH_REQUIRE(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15) == 0, "mmh_pool3x3_fwd: x and y must be 16-byte aligned");
@@ -258,6 +268,10 @@ int mmh_pool3x3_fwd(const float* x, int B, int H, int W, int C, int x_cs, float*
     const dim3 grid((unsigned)mmh::cdiv(total, TPB));
     if (mode == MMH_POOL_MAX)
         hipLaunchKernelGGL(pool3x3_kernel<MMH_POOL_MAX>, grid, dim3(TPB), 0, mmh::as_stream(s), x, B, H, W, C / 4, x_cs, Ho, Wo, y, y_cs);
+    else if (mode == MMH_POOL_AVG_VALID)
+        hipLaunchKernelGGL(pool3x3_kernel<MMH_POOL_AVG_VALID>, grid, dim3(TPB), 0, mmh::as_stream(s), x, B, H, W, C / 4, x_cs, Ho, Wo, y, y_cs);
+    else if (mode == MMH_POOL_MAX_S1)
+        hipLaunchKernelGGL(pool3x3_kernel<MMH_POOL_MAX_S1>, grid, dim3(TPB), 0, mmh::as_stream(s), x, B, H, W, C / 4, x_cs, Ho, Wo, y, y_cs);
     else
         hipLaunchKernelGGL(pool3x3_kernel<MMH_POOL_AVG>, grid, dim3(TPB), 0, mmh::as_stream(s), x, B, H, W, C / 4, x_cs, Ho, Wo, y, y_cs);
     return mmh::check_launch("pool3x3");

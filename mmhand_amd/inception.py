@@ -132,10 +132,16 @@ def pil_bilinear_tables(n_in, n_out):
     return np.stack([first, taps], 1).astype(np.int32), fixed
 
 
-def normalize_lut():
+VARIANTS = ("torchvision", "fid")
+
+
+def normalize_lut(variant="torchvision"):
     """fp32 [3,256]: ToTensor and Normalize (utils.py:26-27) of every byte, evaluated by torch on the CPU exactly as the
-    transforms do - u8.float().div(255).sub(mean).div(std) - so a lookup is bit-identical to them by construction"""
+    transforms do - u8.float().div(255).sub(mean).div(std) - so a lookup is bit-identical to them by construction.
+    variant "fid": pytorch-fid's 2 * (b / 255) - 1 (its ToTensor, then normalize_input), the same for the three channels"""
     u = torch.arange(256, dtype=torch.int32).to(torch.uint8).to(torch.float32).div(255)
+    if variant == "fid":
+        return (2 * u - 1)[None, :].repeat(3, 1).contiguous()
     mean, std = torch.tensor(MEAN, dtype=torch.float32), torch.tensor(STD, dtype=torch.float32)
     return u[None, :].repeat(3, 1).sub(mean[:, None]).div(std[:, None]).contiguous()
 
@@ -143,7 +149,7 @@ def normalize_lut():
 class PreprocessTables:
     """everything mmh_inception_preprocess needs for H x W images: the two passes' tables, the crop window, the lookup table"""
 
-    def __init__(self, H, W_, size=SIZE, device=None):
+    def __init__(self, H, W_, size=SIZE, device=None, variant="torchvision"):
         self.H, self.W, self.size = int(H), int(W_), int(size)
         self.rh, self.rw = resize_size(self.H, self.W, size)
         self.oh = self.ow = int(size)
@@ -153,21 +159,30 @@ class PreprocessTables:
         self.hks, self.vks = int(hk.shape[1]), int(vk.shape[1])
         put = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)     # noqa: E731
         self.hbounds, self.hcoef, self.vbounds, self.vcoef = put(hb), put(hk), put(vb), put(vk)
-        self.lut = normalize_lut().to(device)
+        self.lut = normalize_lut(variant).to(device)
 
 
 # ------------------------------------------------------------------------------------------------- the network
 class InceptionV3:
     """inception.py:61-176 (Inception3, eval, transform_input=False).  forward(x fp32 [B,H,W,4], H, W >= 75; lanes 0..2 the
-    normalised R, G, B, lane 3 zero) -> logits fp32 [B,1000]."""
+    normalised R, G, B, lane 3 zero) -> logits fp32 [B,1000].
 
-    def __init__(self, device=None):
+    variant "fid": pytorch-fid's graph for its pt_inception-2015-12-05 weights (FIDInceptionA / C / E_1 / E_2): the average
+    pools of the A, C and E blocks divide by the number of in-image pixels, Mixed_7c's pool branch is a 3x3 stride-1 max pool,
+    fc may be [1008,2048] and is not used - features() only.  The default variant's launches and bits are what they were."""
+
+    def __init__(self, device=None, variant="torchvision"):
+        if variant not in VARIANTS:
+            raise ValueError(f"InceptionV3: variant {variant!r}: {' | '.join(VARIANTS)}")
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        self.variant = variant
+        self._avg = "avg_valid" if variant == "fid" else "avg"
         self.convs = None
 
     def load_state_dict(self, sd):
         sd = strip_module(sd)
-        missing = [k for k in expected_keys() if k not in sd]
+        fid = self.variant == "fid"
+        missing = [k for k in expected_keys() if k not in sd and not (fid and k.startswith("fc."))]
         if missing:
             raise KeyError(f"InceptionV3: checkpoint lacks {missing[:4]}{' ...' if len(missing) > 4 else ''}")
         convs = {}
@@ -176,9 +191,12 @@ class InceptionV3:
                 raise ValueError(f"InceptionV3: {n}.conv.weight is {tuple(sd[f'{n}.conv.weight'].shape)}, expected {(cout, cin, kh, kw)}")
             w, b = fold_bn(sd[f"{n}.conv.weight"], *(sd[f"{n}.bn.{k}"] for k in BN_KEYS))
             convs[n] = tuple(t.to(self.device) for t in relay_conv(w, b, cin_p=ops.pad4(cin)))
-        if tuple(sd["fc.weight"].shape) != (1000, 2048):
-            raise ValueError(f"InceptionV3: fc.weight is {tuple(sd['fc.weight'].shape)}, expected (1000, 2048)")
-        self.fc = tuple(t.to(self.device) for t in relay_fc(sd["fc.weight"], sd["fc.bias"]))
+        if fid:
+            self.fc = None
+        else:
+            if tuple(sd["fc.weight"].shape) != (1000, 2048):
+                raise ValueError(f"InceptionV3: fc.weight is {tuple(sd['fc.weight'].shape)}, expected (1000, 2048)")
+            self.fc = tuple(t.to(self.device) for t in relay_fc(sd["fc.weight"], sd["fc.bias"]))
         self.convs = convs
         return self
 
@@ -199,7 +217,7 @@ class InceptionV3:
         self._conv(f"{p}.branch1x1", x, 0, out, 0)
         self._chain([f"{p}.branch5x5_1", f"{p}.branch5x5_2"], x, out, 64)
         self._chain([f"{p}.branch3x3dbl_1", f"{p}.branch3x3dbl_2", f"{p}.branch3x3dbl_3"], x, out, 128)
-        self._conv(f"{p}.branch_pool", ops.pool3x3(x, "avg"), 0, out, 224)
+        self._conv(f"{p}.branch_pool", ops.pool3x3(x, self._avg), 0, out, 224)
         return out
 
     def _block_b(self, p, x):
@@ -216,7 +234,7 @@ class InceptionV3:
         self._conv(f"{p}.branch1x1", x, 0, out, 0)
         self._chain([f"{p}.branch7x7_{i}" for i in (1, 2, 3)], x, out, 192)
         self._chain([f"{p}.branch7x7dbl_{i}" for i in (1, 2, 3, 4, 5)], x, out, 384)
-        self._conv(f"{p}.branch_pool", ops.pool3x3(x, "avg"), 0, out, 576)
+        self._conv(f"{p}.branch_pool", ops.pool3x3(x, self._avg), 0, out, 576)
         return out
 
     def _block_d(self, p, x):
@@ -227,7 +245,7 @@ class InceptionV3:
         ops.pool3x3(x, "max", out=out, y_off=512)
         return out
 
-    def _block_e(self, p, x):
+    def _block_e(self, p, x, pool=None):
         B, H, W_, _ = x.shape
         out = ops._empty((B, H, W_, 2048), x)
         self._conv(f"{p}.branch1x1", x, 0, out, 0)
@@ -237,7 +255,7 @@ class InceptionV3:
         t = self._conv(f"{p}.branch3x3dbl_2", self._conv(f"{p}.branch3x3dbl_1", x))
         self._conv(f"{p}.branch3x3dbl_3a", t, 0, out, 1088)
         self._conv(f"{p}.branch3x3dbl_3b", t, 0, out, 1472)
-        self._conv(f"{p}.branch_pool", ops.pool3x3(x, "avg"), 0, out, 1856)
+        self._conv(f"{p}.branch_pool", ops.pool3x3(x, pool or self._avg), 0, out, 1856)
         return out
 
     @torch.no_grad()
@@ -261,12 +279,18 @@ class InceptionV3:
                 x = self._block_c(n, x)
             x = self._block_d("Mixed_7a", x)
             x = self._block_e("Mixed_7b", x)
-            x = self._block_e("Mixed_7c", x)
+            x = self._block_e("Mixed_7c", x, "max_s1" if self.variant == "fid" else None)
         return ops.global_avgpool(x)
 
     @torch.no_grad()
     def forward(self, x):
-        f = self.features(x)
+        return self.logits_of(self.features(x))
+
+    @torch.no_grad()
+    def logits_of(self, f):
+        """features() -> logits: the fc layer alone (one forward serves the Inception score and FID)"""
+        if self.fc is None:
+            raise RuntimeError("InceptionV3: the 'fid' variant has no classifier - features() only")
         wt, b = self.fc
         B = f.shape[0]
         return torch.cat([ops.linear(f[i:i + 64], wt, b) for i in range(0, B, 64)]) if B > 64 else ops.linear(f, wt, b)
@@ -312,6 +336,15 @@ class InceptionScorer:
         if paths is not None and len(paths) != B:
             raise ValueError(f"feed: {B} images, {len(paths)} paths")
         self._logits.append(self.logits(images, layout))
+        self._rows += [dict(r) for r in paths] if paths is not None else [{} for _ in range(B)]
+
+    def feed_features(self, features, paths=None):
+        """feed() for a batch whose pooled features another consumer of the same network already computed (mmhand_amd.fid):
+        only the fc layer runs; the logits are those of feed() on the same images, bit for bit"""
+        B = features.shape[0]
+        if paths is not None and len(paths) != B:
+            raise ValueError(f"feed_features: {B} rows, {len(paths)} paths")
+        self._logits.append(self.net.logits_of(features))
         self._rows += [dict(r) for r in paths] if paths is not None else [{} for _ in range(B)]
 
     def results(self):

@@ -16,7 +16,7 @@ PAD_ZERO, PAD_REFLECT = 0, 1
 ACT_NONE, ACT_RELU, ACT_TANH = 0, 1, 2
 F32, BF16, FP16 = 0, 1, 2
 U8 = 3          # mmh_image_src only
-POOL_MAX, POOL_AVG = 0, 1
+POOL_MAX, POOL_AVG, POOL_AVG_VALID, POOL_MAX_S1 = 0, 1, 2, 3
 
 
 class ConvDesc(C.Structure):
@@ -235,6 +235,10 @@ SIGNATURES = {
     "mmh_global_avgpool": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "mmh_inception_score_ws_bytes": (_sz, [_i, _i]),
     "mmh_inception_score": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "mmh_feature_moments_ws_bytes": (_sz, [_i, _i]),
+    "mmh_feature_moments": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp]),
+    "mmh_poly_mmd_sums_ws_bytes": (_sz, [_i, _i, _i]),
+    "mmh_poly_mmd_sums": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "mmh_heatmap_mse_ws_bytes": (_sz, [_i, _i, _i, _i]),
     "mmh_heatmap_mse": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _d, _vp, _vp, _vp, _i, _vp, _sz, _vp]),
     "mmh_lane_add": (_i, [_vp, _i, _vp, _i, _i64, _i, _vp]),

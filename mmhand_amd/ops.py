@@ -3690,12 +3690,13 @@ def inception_preprocess(images, layout, tables):
 
 def pool3x3(x, mode, c=None, x_off=0, out=None, y_off=0):
     """mode "max": F.max_pool2d(x, 3, 2) (inception.py:131,137,255,333); "avg": F.avg_pool2d(x, 3, 1, 1), always / 9
-    (inception.py:225,299,379).  x fp32 [B,H,W,x_cs], lanes x_off .. x_off + c (default all); out None: a new [B,Ho,Wo,c], else
-    lanes y_off .. y_off + c of out [B,Ho,Wo,y_cs] are written and no other."""
+    (inception.py:225,299,379); pytorch-fid's graph also has "avg_valid": F.avg_pool2d(x, 3, 1, 1, count_include_pad=False) and
+    "max_s1": F.max_pool2d(x, 3, 1, 1).  x fp32 [B,H,W,x_cs], lanes x_off .. x_off + c (default all); out None: a new
+    [B,Ho,Wo,c], else lanes y_off .. y_off + c of out [B,Ho,Wo,y_cs] are written and no other."""
     _chk(x, "x")
     B, H, W_, x_cs = x.shape
     c = x_cs - x_off if c is None else c
-    m = {"max": L.POOL_MAX, "avg": L.POOL_AVG}[mode]
+    m = {"max": L.POOL_MAX, "avg": L.POOL_AVG, "avg_valid": L.POOL_AVG_VALID, "max_s1": L.POOL_MAX_S1}[mode]
     Ho, Wo = ((H - 3) // 2 + 1, (W_ - 3) // 2 + 1) if mode == "max" else (H, W_)
     if x_off % 4 or y_off % 4 or c % 4 or x_off + c > x_cs or Ho < 1 or Wo < 1:
         raise ValueError(f"pool3x3 {mode}: x {tuple(x.shape)} lanes {x_off}+{c}")
@@ -3734,3 +3735,54 @@ def inception_score(logits, classes=None):
     py = torch.empty(classes, dtype=torch.float64, device=logits.device)
     L.call("mmh_inception_score", _ptr(logits), n, cs, classes, _ptr(kl), _ptr(py), _ptr(ws), nbytes, _stream())
     return kl, py
+
+
+# ----------------------------------------------------------------------------- FID / KID reductions (csrc/fid.hip)
+def _chk_features(X, what):
+    if not (X.is_cuda and X.dtype == torch.float32 and X.is_contiguous() and X.dim() == 2 and X.shape[1] % 4 == 0 and
+            X.shape[1] >= 4):
+        raise ValueError(f"{what}: contiguous fp32 CUDA [N,d] features with d a multiple of 4, got {X.dtype} {tuple(X.shape)}")
+
+
+def feature_moments(X, mean=None, cov=None):
+    """X fp32 [N,d] (N >= 2, d % 4 == 0) -> (mean float64 [d], cov float64 [d,d]) on the device: np.mean(X, 0) and
+    np.cov(X, rowvar=False) with float64 accumulation - every cov element one chain of fp64 MFMAs over the rows in order, the
+    lower triangle the mirror of the upper, bit for bit (mmh_feature_moments).  mean / cov: contiguous float64 views to write
+    into (new tensors if None)."""
+    _chk_features(X, "feature_moments")
+    N, d = X.shape
+    nbytes = L.load().mmh_feature_moments_ws_bytes(N, d)
+    if nbytes == 0:
+        raise ValueError(f"feature_moments: N={N} d={d} refused (at least 2 rows)")
+    mean = torch.empty((d,), dtype=torch.float64, device=X.device) if mean is None else mean
+    cov = torch.empty((d, d), dtype=torch.float64, device=X.device) if cov is None else cov
+    for t, shape, name in ((mean, (d,), "mean"), (cov, (d, d), "cov")):
+        if not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and tuple(t.shape) == shape):
+            raise ValueError(f"feature_moments: {name} must be a contiguous float64 CUDA {shape}")
+    ws = torch.empty((nbytes // 8,), dtype=torch.float64, device=X.device)
+    L.call("mmh_feature_moments", _ptr(X), N, d, _ptr(mean), _ptr(cov), _ptr(ws), _stream())
+    return mean, cov
+
+
+def poly_mmd_sums(A, B, idxA, idxB):
+    """A fp32 [Na,d], B fp32 [Nb,d] on the device; idxA [S,Ma], idxB [S,Mb]: HOST integer arrays of row numbers (checked
+    here against Na / Nb, then uploaded) -> float64 [S,3] on the device: per subset the sums over p != q (by list position) of
+    k(a_p, a_q) and of k(b_p, b_q), and over all p, q of k(a_p, b_q), k(x, y) = (x.y / d + 1)^3 (mmh_poly_mmd_sums)."""
+    _chk_features(A, "poly_mmd_sums A")
+    _chk_features(B, "poly_mmd_sums B")
+    if A.shape[1] != B.shape[1] or A.device != B.device:
+        raise ValueError(f"poly_mmd_sums: A {tuple(A.shape)} and B {tuple(B.shape)}: one feature width, one device")
+    ia, ib = (np.ascontiguousarray(np.asarray(i.cpu() if torch.is_tensor(i) else i), dtype=np.int64) for i in (idxA, idxB))
+    if ia.ndim != 2 or ib.ndim != 2 or ia.shape[0] != ib.shape[0] or ia.size == 0 or ib.size == 0:
+        raise ValueError(f"poly_mmd_sums: index lists {ia.shape} and {ib.shape}: [S,Ma] and [S,Mb], none empty")
+    if ia.min() < 0 or ia.max() >= A.shape[0] or ib.min() < 0 or ib.max() >= B.shape[0]:
+        raise ValueError(f"poly_mmd_sums: an index names no row of A [{A.shape[0]}] / B [{B.shape[0]}]")
+    S, Ma, Mb, d = ia.shape[0], ia.shape[1], ib.shape[1], A.shape[1]
+    nbytes = L.load().mmh_poly_mmd_sums_ws_bytes(S, Ma, Mb)
+    if nbytes == 0:
+        raise ValueError(f"poly_mmd_sums: S={S} Ma={Ma} Mb={Mb} refused")
+    da, db = (torch.from_numpy(i.astype(np.int32)).to(A.device) for i in (ia, ib))
+    ws = torch.empty((nbytes // 8,), dtype=torch.float64, device=A.device)
+    out = torch.empty((S, 3), dtype=torch.float64, device=A.device)
+    L.call("mmh_poly_mmd_sums", _ptr(A), _ptr(B), d, _ptr(da), _ptr(db), S, Ma, Mb, _ptr(out), _ptr(ws), _stream())
+    return out
