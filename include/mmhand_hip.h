@@ -1118,6 +1118,35 @@ int mmh_render_pose_depth(const double* xyz0, const double* xyz1, int N, int H, 
 size_t mmh_hpe_normalize_ws_bytes(int B, int H, int W);
 int mmh_hpe_normalize(const mmh_image_src* src, int B, int H, int W, void* ws, size_t ws_bytes, float* out, mmh_stream_t s);
 
+/* an addition (train_hpe --augment_geom / --augment_color): the reference trains its estimators on the files' pixels as they
+ * are (RHD_dataset.py:215-263 has no augmentation); this is the conventional one - rotate / scale / shift / flip and a colour
+ * jitter - fused with the min-max normalisation above, which has to FOLLOW the colour operations and be taken over the
+ * warped output: it cancels every brightness or contrast change that is one affine map of the three channels together.
+ *   img    uint8 [B,Hs,Ws,3] BGR, as the loader reads PNGs
+ *   xf     device float64 [B,6] = [a00 a01 a02; a10 a11 a12] per image, or NULL = identity (needs Ho == Hs, Wo == Ws)
+ *   cm     device float64 [B,9], row-major on (R,G,B), or NULL = identity
+ *   gamma  device float64 [B], > 0, or NULL = 1
+ *   out    fp32 [B,Ho,Wo,4]: lanes 0..2 = R,G,B, lane 3 = 0 (one 16-byte store per pixel); 16-byte aligned
+ * Per image b and output pixel (x, y), everything in float64:
+ *  1. sample: the source coordinate, the clamp (edge replicate, a NaN lands on 0), the taps and the weights are exactly
+ *     mmh_decode_inputs_affine's (the text at that entry; no fused multiply-add in the coordinate); per channel
+ *     (1 - wy) * ((1 - wx) * v00 + wx * v01) + wy * ((1 - wx) * v10 + wx * v11) over the four raw bytes gives R, G, B in [0, 255]
+ *  2. colour matrix: v_c = (cm[3c]*R + cm[3c+1]*G) + cm[3c+2]*B, each product and sum rounded on its own, clamped to [0, 255]
+ *     (a NaN to 0)
+ *  3. gamma: if gamma[b] != 1, v_c = 255 * pow(v_c / 255, gamma[b]); if it is 1 (or NULL) pow is not called
+ *  4. normalise: mn / mx = the smallest / largest v_c over all output pixels and the three channels of image b;
+ *     out = (float)((v - mn) / (mx - mn)), one rounding; mx == mn gives zeros
+ * With xf, cm and gamma NULL or identity the result is bit-identical to mmh_hpe_normalize of the same bytes in "bgr_hwc"
+ * order; an integer shift, a flip or a quarter turn has weights 0 and a permutation or power-of-two cm is exact.  The matrices
+ * and gamma are the caller's to keep finite (gamma positive): nothing they hold can index outside the image.  Two passes over
+ * the source (reduce, then recompute and write), partials merged through ws, no atomics; every byte offset is 64-bit.
+ * ws: mmh_hpe_augment_normalize_ws_bytes(B, Ho, Wo) bytes (0 = refused), 8-byte aligned as xf, cm and gamma are.  Non-positive
+ * sizes, xf == NULL with differing sizes, a workspace that is too small and a misaligned buffer return non-zero before any
+ * launch.                                                                                                                  */
+size_t mmh_hpe_augment_normalize_ws_bytes(int B, int Ho, int Wo);
+int mmh_hpe_augment_normalize(const void* img, int B, int Hs, int Ws, int Ho, int Wo, const double* xf, const double* cm,
+                              const double* gamma, void* ws, size_t ws_bytes, float* out, mmh_stream_t s);
+
 /* replaces networks/net_hpm2d.py:69,118 (nn.Upsample(scale_factor=8, mode='bilinear', align_corners=True)) and
  * hpe_estimator.py:127-135 (torch.max of every joint's map, index -> pixel).
  * heat: fp32 [B][h][w][cs], cs >= 21, joints in lanes 0..20.  up: fp32 [B][8h][8w][24], lanes 21..23 zero (the input of

@@ -7,6 +7,7 @@
 #include <algorithm>
 #include <cmath>
 #include "device_prims.h"
+#include "affine_sample.h"
 
 namespace mmh { int g_pw_v2 = 1; int g_col_chunks = 2048; int g_row_chunks = 4096; }
 // mmh_set_dropout_salt: a device uint64 that every dropout-drawing kernel adds to its by-value seed when it runs (NULL = none).
@@ -1964,7 +1965,7 @@ __global__ void decode_inputs_kernel(const uint8_t* __restrict__ img1, const uin
 // rounding, at the store.  The joints arrive scaled to the output grid, so the pose maps are heat() on output pixels.
 // One float4 per lane, 15 lanes per output pixel (x_h1, x_h2, 2 of x_d, 11 of x_p = 240 bytes), so that a wave's stores
 // into x_p are contiguous.
-struct ResizeTap { int i0, i1; double w; };
+// (ResizeTap and lerp2 live in affine_sample.h.)
 __device__ __forceinline__ ResizeTap resize_tap(int o, int n_src, int n_out) {
     double s = ((double)o + 0.5) * (double)n_src / (double)n_out - 0.5;
     if (s < 0.0) s = 0.0;
@@ -1973,9 +1974,6 @@ __device__ __forceinline__ ResizeTap resize_tap(int o, int n_src, int n_out) {
     t.i1 = min(t.i0 + 1, n_src - 1);
     t.w = s - (double)t.i0;
     return t;
-}
-__device__ __forceinline__ double lerp2(double v00, double v01, double v10, double v11, double wx, double wy) {
-    return (1.0 - wy) * ((1.0 - wx) * v00 + wx * v01) + wy * ((1.0 - wx) * v10 + wx * v11);
 }
 __device__ __forceinline__ float norm_f64(double v) { return (float)((v / 255.0 - 0.5) / 0.5); }
 __device__ __forceinline__ double depth_raw(const uint8_t* p) { return 256.0 * (double)p[1] + (double)p[2]; }
@@ -2052,37 +2050,8 @@ __global__ void decode_inputs_resized_kernel(const uint8_t* __restrict__ img1, c
 
 // The same pass sampling through a per-image, per-side inverse affine map instead of the axis-aligned resize
 // (mmh_decode_inputs_affine; --augment_geom): a = [a00 a01 a02; a10 a11 a12] takes the output pixel (x, y) to the source
-// coordinate sx = (a00 x + a01 y) + a02, sy = (a10 x + a11 y) + a12.  Every product and sum is rounded on its own
-// (contraction off), so the coordinates - and with them taps and weights - are numpy's bit for bit.  Edge replicate: the
-// coordinate is clamped to [0, n - 1] BEFORE it becomes an integer; the comparisons are written so that a NaN lands on 0,
-// and the integer is clamped once more, so no matrix whatever can index outside the image.
-__device__ __forceinline__ void affine_coord(const double* __restrict__ a, int x, int y, double& sx, double& sy) {
-#pragma clang fp contract(off)
-    const double fx = (double)x, fy = (double)y;
-    sx = (a[0] * fx + a[1] * fy) + a[2];
-    sy = (a[3] * fx + a[4] * fy) + a[5];
-}
-__device__ __forceinline__ ResizeTap affine_tap(double s, int n_src) {
-    const double hi = (double)(n_src - 1);
-    s = s > 0.0 ? s : 0.0;                   // NaN compares false: 0
-    s = s < hi ? s : hi;
-    ResizeTap t;
-    t.i0 = max(0, min((int)s, n_src - 1));   // 0 <= s <= n - 1: the cast is the floor
-    t.i1 = min(t.i0 + 1, n_src - 1);
-    t.w = s - (double)t.i0;
-    return t;
-}
-struct AffineTaps { int64_t o00, o01, o10, o11; double wx, wy; };
-__device__ __forceinline__ AffineTaps affine_taps(const double* __restrict__ a, int x, int y, int Hs, int Ws) {
-    double sx, sy;
-    affine_coord(a, x, y, sx, sy);
-    const ResizeTap tx = affine_tap(sx, Ws), ty = affine_tap(sy, Hs);
-    const int64_t row0 = (int64_t)ty.i0 * Ws, row1 = (int64_t)ty.i1 * Ws;
-    AffineTaps t;
-    t.o00 = (row0 + tx.i0) * 3, t.o01 = (row0 + tx.i1) * 3, t.o10 = (row1 + tx.i0) * 3, t.o11 = (row1 + tx.i1) * 3;
-    t.wx = tx.w, t.wy = ty.w;
-    return t;
-}
+// coordinate sx = (a00 x + a01 y) + a02, sy = (a10 x + a11 y) + a12; the rule - no contraction, edge replicate, a NaN on
+// 0 - and its device functions affine_coord, affine_tap and affine_taps are affine_sample.h's.
 __device__ __forceinline__ float depth_affine(const uint8_t* __restrict__ dep, const AffineTaps& t) {
     return depth_f64(lerp2(depth_raw(dep + t.o00), depth_raw(dep + t.o01), depth_raw(dep + t.o10), depth_raw(dep + t.o11),
                            t.wx, t.wy));

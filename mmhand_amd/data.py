@@ -47,7 +47,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .options import check_augment, check_depth_source, check_resize_inputs
+from .options import check_augment, check_augment_color, check_depth_source, check_resize_inputs
 
 
 class SyntheticHandLoader:
@@ -323,6 +323,47 @@ def augment_draws(n_items, epoch, opt):
     d[..., 4] = u[..., 4] < flip
     if pair == "shared":
         d[:, 1] = d[:, 0]
+    return d
+
+
+# ----------------------------------------------------------------------------- colour jitter: host-side maths
+# train_hpe --augment_color.  The estimators' input is min-max normalised per image, which cancels any change of brightness or
+# contrast that is one affine map of the three channels together; what is left to vary is what mixes channels (saturation,
+# hue, per-channel gains) or is non-linear (gamma).  Matrices act on column vectors (R, G, B).
+_LUMA = (0.299, 0.587, 0.114)
+_HUE_K = ((0.0, -1.0, 1.0), (1.0, 0.0, -1.0), (-1.0, 1.0, 0.0))
+
+
+def color_matrix(saturation, hue_deg, gains):
+    """float64 [..., 3, 3] = diag(gains) @ Hue(hue_deg) @ Sat(saturation), broadcasting saturation [...], hue_deg [...] and
+    gains [..., 3].  Sat(s) = s I + (1 - s) 1 [0.299 0.587 0.114] (towards the luma grey), Hue(h) = cos h I + (1 - cos h) / 3 11^T
+    + sin h / sqrt(3) K with K = [[0,-1,1],[1,0,-1],[-1,1,0]] (a rotation about the grey axis).  Both are closed forms that are
+    the exact identity at the neutral value (s = 1; h a multiple of 360), so (1, 0, (1,1,1)) gives the identity bit for bit."""
+    gains = np.asarray(gains, dtype=np.float64)
+    if gains.shape[-1:] != (3,):
+        raise ValueError(f"color_matrix: gains [..., 3] expected, got {gains.shape}")
+    s, h, g0 = np.broadcast_arrays(np.asarray(saturation, dtype=np.float64), np.asarray(hue_deg, dtype=np.float64), gains[..., 0])
+    gains = np.broadcast_to(gains, s.shape + (3,))
+    eye, ones, K = np.eye(3), np.ones((3, 3)), np.array(_HUE_K)
+    cos, sin = _cos_sin_deg(h)
+    s, cos, sin = s[..., None, None], cos[..., None, None], sin[..., None, None]
+    sat = s * eye + (1.0 - s) * (np.ones((3, 1)) @ np.array([_LUMA]))
+    hue = cos * eye + (1.0 - cos) / 3.0 * ones + sin / math.sqrt(3.0) * K
+    return gains[..., :, None] * (hue @ sat)
+
+
+def color_draws(n_items, epoch, opt):
+    """The colour draws of one epoch for the WHOLE dataset, float64 [n_items, 6] = (saturation, hue in degrees, gain_R, gain_G,
+    gain_B, gamma) per item, from np.random.default_rng([aug_seed, epoch, 1]): a stream of its own, so switching colour on does
+    not change augment_draws' geometry and vice versa.  Indexed by dataset item, as augment_draws is.  s ~ U(1 - a, 1 + a)
+    clipped at 0, h ~ U(-d, d), gain ~ U(1 - g, 1 + g), gamma = exp(U(-q, q))."""
+    sat, hue, gain, gamma, seed = check_augment_color(opt)
+    u = 2.0 * np.random.default_rng([int(seed), int(epoch), 1]).random((int(n_items), 6)) - 1.0
+    d = np.empty_like(u)
+    d[:, 0] = np.maximum(1.0 + u[:, 0] * sat, 0.0)
+    d[:, 1] = u[:, 1] * hue
+    d[:, 2:5] = 1.0 + u[:, 2:5] * gain
+    d[:, 5] = np.exp(u[:, 5] * gamma)
     return d
 
 

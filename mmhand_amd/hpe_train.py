@@ -377,7 +377,11 @@ class Hpm2dTrainer(_PoseTrainer):
 
     def step(self, images, uv, layout="nchw", lr=None):
         """normalise -> forward -> loss -> backward -> Adam; -> the six losses, float64 [6] on the device"""
-        x = ops.hpe_normalize(images, layout)
+        return self.step_normalized(ops.hpe_normalize(images, layout), uv, lr=lr)
+
+    def step_normalized(self, x, uv, lr=None):
+        """step() from the network's input on: x fp32 [B,H,W,4] as ops.hpe_normalize or ops.hpe_augment_normalize leave it, uv
+        the joints in pixels of THAT input (after any warp)"""
         self.forward(x)
         losses, G = self.loss(uv)
         self.backward(G)

@@ -222,6 +222,8 @@ SIGNATURES = {
     "mmh_render_pose_depth": (_i, [_vp, _vp, _i, _i, _i, _d, _d, _vp, _i, _vp]),
     "mmh_hpe_normalize_ws_bytes": (_sz, [_i, _i, _i]),
     "mmh_hpe_normalize": (_i, [C.POINTER(ImageSrc), _i, _i, _i, _vp, _sz, _vp, _vp]),
+    "mmh_hpe_augment_normalize_ws_bytes": (_sz, [_i, _i, _i]),
+    "mmh_hpe_augment_normalize": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
     "mmh_heatmap_upsample_argmax_ws_bytes": (_sz, [_i, _i, _i]),
     "mmh_heatmap_upsample_argmax": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "mmh_linear_chunks": (_i, [_i]),

@@ -3513,6 +3513,43 @@ def hpe_normalize(images, layout="nchw"):
     return out
 
 
+def hpe_augment_normalize(images, xf=None, cm=None, gamma=None, out_size=None):
+    """hpe_normalize(images, "bgr_hwc") of a uint8 [B,H,W,3] BGR batch under conventional augmentation, one fused pass
+    (mmh_hpe_augment_normalize; train_hpe --augment_geom / --augment_color): xf float64 [B,6] or [B,2,3] = one sampling matrix
+    per image (data.affine_inverse: output pixel -> source coordinate; bilinear, edge replicate, as decode_inputs_affine), cm
+    float64 [B,9] or [B,3,3] = one colour matrix per image on (R,G,B) (data.color_matrix), gamma float64 [B] > 0; each may be
+    None = identity.  The minimum and maximum are taken AFTER warp, matrix, clamp to [0, 255] and gamma, over the output of
+    out_size (None = the images' size; another size needs xf).  -> fp32 [B,Ho,Wo,4], lanes 0..2 = R,G,B, lane 3 zero.  With
+    everything None or identity: bit-identical to hpe_normalize(images, "bgr_hwc").  The matrices and gamma are the caller's
+    to keep finite (data.affine_inverse refuses others); the kernel clamps whatever it is given."""
+    if not torch.is_tensor(images) or not images.is_cuda or images.dtype != torch.uint8 or images.dim() != 4 or \
+            images.shape[3] != 3 or not images.is_contiguous():
+        raise ValueError("hpe_augment_normalize: expected a contiguous uint8 CUDA tensor [B,H,W,3] (BGR), got "
+                         f"{getattr(images, 'dtype', type(images))} {tuple(getattr(images, 'shape', ()))}")
+    B, H, W_, _ = images.shape
+    dev = images.device
+
+    def rows(t, n, alt, name):
+        if t is None:
+            return None
+        assert torch.is_tensor(t) and t.dtype == torch.float64 and t.device == dev and t.is_contiguous() and \
+            tuple(t.shape) in ((B, n), (B,) + alt), f"{name}: contiguous float64 [B,{n}] on the images' device"
+        return t
+
+    xf, cm, gamma = rows(xf, 6, (2, 3), "xf"), rows(cm, 9, (3, 3), "cm"), rows(gamma, 1, (), "gamma")
+    Ho, Wo = resize_size(out_size, (H, W_)) or (H, W_)
+    if xf is None and (Ho, Wo) != (H, W_):
+        raise ValueError(f"hpe_augment_normalize: out_size {(Ho, Wo)} differs from the images' {(H, W_)}: that needs xf")
+    nbytes = L.load().mmh_hpe_augment_normalize_ws_bytes(B, Ho, Wo)
+    if nbytes == 0:
+        raise ValueError(f"hpe_augment_normalize: shape {tuple(images.shape)} -> {(Ho, Wo)} refused")
+    ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=dev)
+    out = torch.empty((B, Ho, Wo, 4), dtype=torch.float32, device=dev)
+    L.call("mmh_hpe_augment_normalize", _ptr(images), B, H, W_, Ho, Wo, _ptr(xf), _ptr(cm), _ptr(gamma), _ptr(ws), nbytes,
+           _ptr(out), _stream())
+    return out
+
+
 def heatmap_upsample_argmax(heat):
     """heat: fp32 [B,h,w,cs] (cs >= 21, joints in lanes 0..20) -> (up fp32 [B,8h,8w,24], xy int32 [B,21,2], peak fp32 [B,21]):
     nn.Upsample(scale_factor=8, bilinear, align_corners=True) (net_hpm2d.py:69,118) with lanes 21..23 zero, and per joint

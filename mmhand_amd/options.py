@@ -269,6 +269,36 @@ def check_augment(opt):
     return rotate, scale, shift, flip, pair, seed
 
 
+def check_augment_color(opt):
+    """--augment_color of train_hpe and its ranges, validated; absent attributes are the defaults.  Returns None when the flag
+    is off, else (saturation, hue, gain, gamma, seed): s ~ U(1 - a, 1 + a) clipped at 0, h ~ U(-d, d) degrees,
+    gain ~ U(1 - g, 1 + g) per channel, gamma = exp(U(-q, q))."""
+    if not getattr(opt, "augment_color", False):
+        return None
+
+    def num(name, default):
+        v = getattr(opt, name, default)
+        v = default if v is None else v
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or v != v or v in (float("inf"), float("-inf")):
+            raise ValueError(f"--{name} {v!r}: a finite number expected")
+        return float(v)
+
+    sat, hue, gain, gamma = num("aug_saturation", 0.3), num("aug_hue", 10.0), num("aug_gain", 0.1), num("aug_gamma", 0.2)
+    if sat < 0.0:
+        raise ValueError(f"--aug_saturation {sat!r}: expected a >= 0 (s ~ U(1 - a, 1 + a), clipped at 0)")
+    if not 0.0 <= hue <= 180.0:
+        raise ValueError(f"--aug_hue {hue!r}: expected degrees in [0, 180]")
+    if not 0.0 <= gain < 1.0:
+        raise ValueError(f"--aug_gain {gain!r}: expected 0 <= g < 1 (a gain ~ U(1 - g, 1 + g) must stay positive)")
+    if not 0.0 <= gamma <= 4.0:
+        raise ValueError(f"--aug_gamma {gamma!r}: expected 0 <= q <= 4 (gamma = exp(U(-q, q)))")
+    seed = getattr(opt, "aug_seed", 0)
+    seed = 0 if seed is None else seed
+    if isinstance(seed, bool) or not isinstance(seed, int) or seed < 0:
+        raise ValueError(f"--aug_seed {seed!r}: a non-negative integer expected")
+    return sat, hue, gain, gamma, seed
+
+
 class BaseOptions:
     isTrain = None
     _extra = []

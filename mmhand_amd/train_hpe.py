@@ -5,6 +5,8 @@ directories, on the device.
         [--checkpoints_dir ./checkpoints] [--batchSize 32] [--niter 100] [--niter_decay 100] [--lr 1e-4] [--beta1 0.9]
         [--sigma 5] [--stage_weights 1 1 1 1 1 1] [--init_from PTH | --init_seed N] [--val_dataroot DIR] [--save_epoch_freq 5]
         [--smooth_l1_beta 1.0] [--loss_scale 10] [--heat_source target|predicted] [--hpm2d PTH]
+        [--augment_geom [--aug_rotate 15] [--aug_scale 0.1] [--aug_shift 0.05] [--aug_flip 0]] [--aug_seed 0]
+        [--augment_color [--aug_saturation 0.3] [--aug_hue 10] [--aug_gain 0.1] [--aug_gamma 0.2]]
 
 `--extra_dataroot` (repeatable) adds prepared directories such as `aug --novel` output to the training list: the paper's
 "real + generated" mix.  The labels are the directories' annotations; the learning rate follows the reference's linear rule
@@ -14,7 +16,7 @@ models/networks/__init__.py:72).  The parse-time defaults `--lr 1e-4 --beta1 0.9
 reference's values to train as it does.
 
 `--net hpm2d` (the default).  Images are read as `evaluate --pck_images` reads them (data._read_bgr, here on loader threads), go
-to the device as bytes and through mmh_hpe_normalize.  The loss is the sum over the six stage outputs of --stage_weights[s] times
+to the device as bytes and through mmh_hpe_normalize (mmh_hpe_augment_normalize under the augmentation flags, below).  The loss is the sum over the six stage outputs of --stage_weights[s] times
 the MSE against the sigma-5 Gaussian target; the reference's own (hpm2d_model.py:143-151) is that sum times 1000 =
 `--stage_weights 1000 1000 1000 1000 1000 1000`; the default weights of 1 are this port's.  `--val_dataroot` scores the current
 weights after every epoch with hpe.HPEstimator (the 2D PCK figures of `evaluate --pck_images`).  Writes
@@ -33,7 +35,19 @@ by the factor 700; this port trains what its evaluator scores.]  `--val_dataroot
 --hpm2d, `pck3d_auc` / `epe3d_mean` of hpe.HPEstimator(hpm2d, the current weights).  --init_seed sizes depth_fc_1 for the first
 training image (height / 8; square, a multiple of 8).  --batchSize is at most 64 (the Linear kernels' rows); --stage_weights
 does not apply.  Writes latest_net_Hpm3d.pth / <epoch>_net_Hpm3d.pth, the names the reference's evaluator loads and what
-`evaluate --pck --hpm3d` takes."""
+`evaluate --pck --hpm3d` takes.
+
+`--augment_geom` / `--augment_color` (additions; off: every epoch shows the network the files' pixels, as the reference does):
+conventional augmentation of the TRAINING images, the row a "real + generated" table is compared with.  Per epoch and item - an
+item's number is its position in the training list before the epoch's shuffle - the host draws a rotation, scale, shift (and
+flip) from (aug_seed, epoch) (data.augment_draws, side 0; the names, defaults and checks of `train`) and a saturation, hue,
+three channel gains and a gamma from a stream of their own (data.color_draws), so either switch leaves the other's draws as
+they are.  The images go through ops.hpe_augment_normalize instead of ops.hpe_normalize - one fused pass that warps, applies
+the colour matrix and the gamma curve and takes the min-max normalisation after them (it would cancel a plain brightness or
+contrast change) - and the joints through data.affine_joints, so the targets the device builds from them follow the warp.
+`--net hpm3d --heat_source target` has no image: --augment_geom moves the joints its maps are rendered from and
+--augment_color is refused; with `--heat_source predicted` the augmented images feed --hpm2d and the depth labels stay (a 2D
+warp).  Validation is never augmented."""
 import argparse
 import json
 import os
@@ -48,6 +62,17 @@ from . import hpe_train
 
 # the widths --init_seed builds (the reference's: networks/net_hpm2d.py:40-67, net_hpm3d.py:29-64); tests narrow them
 INIT_WIDTHS = hpe_train.FULL_WIDTHS
+
+
+# (flag, default, help) of the ranges behind each switch; the geometric ones are `train`'s (options.py)
+GEOM_FLAGS = [("aug_rotate", 15.0, "with --augment_geom: degrees, theta ~ U(-r, r)"),
+              ("aug_scale", 0.1, "with --augment_geom: s ~ U(1 - a, 1 + a), 0 <= a < 1"),
+              ("aug_shift", 0.05, "with --augment_geom: shift ~ U(-f, f) of the image size, per axis"),
+              ("aug_flip", 0.0, "with --augment_geom: probability of a horizontal flip (a mirrored hand is the other hand)")]
+COLOR_FLAGS = [("aug_saturation", 0.3, "with --augment_color: s ~ U(1 - a, 1 + a), clipped at 0"),
+               ("aug_hue", 10.0, "with --augment_color: degrees about the grey axis, h ~ U(-d, d)"),
+               ("aug_gain", 0.1, "with --augment_color: per channel, gain ~ U(1 - g, 1 + g)"),
+               ("aug_gamma", 0.2, "with --augment_color: gamma = exp(U(-q, q))")]
 
 
 def build_parser():
@@ -78,6 +103,16 @@ def build_parser():
                                                                "under this seed (default 0 when --init_from is not given)")
     p.add_argument("--val_dataroot", default=None, help="prepared directory scored with the current weights after every epoch")
     p.add_argument("--save_epoch_freq", type=int, default=5)
+    p.add_argument("--augment_geom", action="store_true",
+                   help="a random rotation, scale, shift (and flip) per training image and epoch, inside the normalisation pass "
+                        "(mmh_hpe_augment_normalize; bilinear, edge replicate); the joints follow")
+    for flag, default, text in GEOM_FLAGS + COLOR_FLAGS:
+        p.add_argument("--" + flag, type=float, default=None, help=f"{text} (default {default})")
+    p.add_argument("--augment_color", action="store_true",
+                   help="a random saturation, hue, gain per channel and gamma per training image and epoch, in the same pass; the "
+                        "min-max normalisation is taken after them")
+    p.add_argument("--aug_seed", type=int, default=None, help="with --augment_geom / --augment_color: seed of the draws (with "
+                                                              "the epoch number; default 0)")
     p.add_argument("--seed", type=int, default=0, help="the seed of the epochs' shuffles")
     p.add_argument("--threads", type=int, default=8, help="image-reading threads")
     p.add_argument("--gpu", type=int, default=0)
@@ -111,6 +146,29 @@ def check_args(parser, a):
             parser.error("--heat_source predicted needs --hpm2d <checkpoint of the 2D hand-pose machine>")
     elif a.hpm2d or a.heat_source != "target" or a.smooth_l1_beta != 1.0 or a.loss_scale != 10.0:
         parser.error("--hpm2d, --heat_source, --smooth_l1_beta and --loss_scale belong to --net hpm3d")
+    check_augment_args(parser, a)
+
+
+def check_augment_args(parser, a):
+    """the augmentation flags: a range without its switch is an error; the defaults are filled in (they land in the log)"""
+    from .options import check_augment, check_augment_color
+    for switch, flags in (("augment_geom", GEOM_FLAGS), ("augment_color", COLOR_FLAGS)):
+        for flag, default, _ in flags:
+            if getattr(a, flag) is None:
+                setattr(a, flag, default)
+            elif not getattr(a, switch):
+                parser.error(f"--{flag} does nothing without --{switch}")
+    if a.aug_seed is None:
+        a.aug_seed = 0
+    elif not (a.augment_geom or a.augment_color):
+        parser.error("--aug_seed does nothing without --augment_geom or --augment_color")
+    if a.augment_color and a.net == "hpm3d" and a.heat_source == "target":
+        parser.error("--augment_color: --net hpm3d --heat_source target reads no image (its maps are rendered from the joints)")
+    try:
+        check_augment(a)
+        check_augment_color(a)
+    except ValueError as e:
+        parser.error(str(e))
 
 
 def _loader(root, a, dev):
@@ -133,8 +191,56 @@ def labelled_images(roots, a, dev, with_depth=False):
     return out
 
 
-def batches(items, batch, pool, dev):
-    """-> (images uint8 [B,H,W,3] BGR on the device, uv [B,21,2]) per batch, the next batch's files being read meanwhile"""
+class Augment:
+    """--augment_geom / --augment_color for the training list of `n_items`: one epoch's draws for every item (set_epoch), applied
+    to a batch by the items' numbers - what an image gets depends on (aug_seed, epoch, item) and on nothing else"""
+
+    def __init__(self, a, n_items):
+        self.a, self.n = a, int(n_items)
+        self.geom = self.color = None
+
+    @classmethod
+    def of(cls, a, n_items):
+        return cls(a, n_items) if a.augment_geom or a.augment_color else None
+
+    def set_epoch(self, epoch):
+        from .data import augment_draws, color_draws
+        self.geom = augment_draws(self.n, epoch, self.a)[:, 0] if self.a.augment_geom else None      # side 0
+        self.color = color_draws(self.n, epoch, self.a) if self.a.augment_color else None
+
+    def forward_maps(self, ids, src):
+        """-> the forward matrices float64 [B,2,3] of these items on the src = (H, W) grid, or None without --augment_geom"""
+        from .data import affine_forward
+        if self.geom is None:
+            return None
+        d = self.geom[np.asarray(ids, dtype=np.int64)]
+        return affine_forward(d[:, 0], d[:, 1], d[:, 2], d[:, 3], d[:, 4], src)
+
+    def joints(self, uv, ids, src):
+        """uv [B,21,2] of the files -> on the warped images"""
+        from .data import affine_joints
+        fwd = self.forward_maps(ids, src)
+        return uv if fwd is None else affine_joints(uv, fwd, src)
+
+    def normalize(self, images, ids):
+        """images uint8 [B,H,W,3] BGR on the device -> the estimators' input fp32 [B,H,W,4] (ops.hpe_augment_normalize)"""
+        from . import ops
+        from .data import affine_inverse, color_matrix
+        src, dev = tuple(images.shape[1:3]), images.device
+        fwd = self.forward_maps(ids, src)
+        xf = cm = gamma = None
+        if fwd is not None:
+            xf = torch.from_numpy(affine_inverse(fwd, src).reshape(-1, 6)).to(dev)
+        if self.color is not None:
+            c = self.color[np.asarray(ids, dtype=np.int64)]
+            cm = torch.from_numpy(color_matrix(c[:, 0], c[:, 1], c[:, 2:5]).reshape(-1, 9)).to(dev)
+            gamma = torch.from_numpy(np.ascontiguousarray(c[:, 5])).to(dev)
+        return ops.hpe_augment_normalize(images, xf, cm, gamma)
+
+
+def batches(items, batch, pool, dev, ids=None):
+    """-> (images uint8 [B,H,W,3] BGR on the device, uv [B,21,2]) per batch, the next batch's files being read meanwhile; with
+    `ids` (one number per item, for Augment) -> (images, uv, the batch's numbers)"""
     from .data import _read_bgr
     chunks = [items[i:i + batch] for i in range(0, len(items), batch)]
     pending = [pool.submit(_read_bgr, it[0]) for it in chunks[0]] if chunks else []
@@ -143,7 +249,8 @@ def batches(items, batch, pool, dev):
         pending = [pool.submit(_read_bgr, it[0]) for it in chunks[i + 1]] if i + 1 < len(chunks) else []
         if any(im.shape != imgs[0].shape for im in imgs):
             raise SystemExit(f"train_hpe: images of different sizes in one batch ({chunk[0][0]} ...)")
-        yield torch.from_numpy(np.stack(imgs)).to(dev), np.stack([it[1] for it in chunk])
+        out = torch.from_numpy(np.stack(imgs)).to(dev), np.stack([it[1] for it in chunk])
+        yield out if ids is None else out + (list(ids[i * batch:(i + 1) * batch]),)
 
 
 def validate(trainer, items, a, pool, dev):
@@ -156,22 +263,27 @@ def validate(trainer, items, a, pool, dev):
 
 
 # ------------------------------------------------------------------------------------------------- --net hpm3d
-def batches_3d(items, a, pool, dev, hpm2d):
+def batches_3d(items, a, pool, dev, hpm2d, aug=None, ids=None, size=None):
     """-> (the network's input: uv [B,21,2] under --heat_source target - no file is opened - or the 2D machine's upsampled maps
-    fp32 [B,H,W,24]; the target depths [B,21]; the images or None) per batch"""
+    fp32 [B,H,W,24]; the target depths [B,21]; the images or None) per batch.  aug (an Augment, with the items' numbers `ids`):
+    the training epoch's augmentation - the joints moved on the size x size grid, or the images in front of the 2D machine"""
     from . import hpe, ops
     zs = hpe.Z_SCALE[a.dataset] / 256.0
     if a.heat_source == "target":
         for i in range(0, len(items), a.batchSize):
             chunk = items[i:i + a.batchSize]
-            yield np.stack([it[1] for it in chunk]), np.stack([it[2] for it in chunk]) * zs, None
+            uv = np.stack([it[1] for it in chunk])
+            if aug is not None:
+                uv = aug.joints(uv, ids[i:i + a.batchSize], (size, size))
+            yield uv, np.stack([it[2] for it in chunk]) * zs, None
         return
     at = 0
     for images, _ in batches(items, a.batchSize, pool, dev):
         chunk = items[at:at + images.shape[0]]
-        at += images.shape[0]
         with torch.no_grad():
-            up = ops.heatmap_upsample_argmax(hpm2d(ops.hpe_normalize(images, "bgr_hwc")))[0]
+            x = ops.hpe_normalize(images, "bgr_hwc") if aug is None else aug.normalize(images, ids[at:at + images.shape[0]])
+            up = ops.heatmap_upsample_argmax(hpm2d(x))[0]
+        at += images.shape[0]
         yield up, np.stack([it[2] for it in chunk]) * zs, images
 
 
@@ -223,14 +335,17 @@ def main_3d(a):
         trainer.load_state_dict(hpe_train.init_state_dict_3d(a.init_seed or 0, INIT_WIDTHS, head_hw))
     out_dir = os.path.join(a.checkpoints_dir, a.name)
     os.makedirs(out_dir, exist_ok=True)
-    rng, log = random.Random(a.seed), []
+    rng, log, aug = random.Random(a.seed), [], Augment.of(a, len(train))
     with ThreadPoolExecutor(a.threads) as pool:
         for epoch in range(1, a.niter + a.niter_decay + 1):
             lr = hpe_train.linear_lr(a.lr, epoch - 1, a.niter, a.niter_decay)
-            order = list(train)
-            rng.shuffle(order)
+            ids = list(range(len(train)))
+            rng.shuffle(ids)                                        # the permutation list(train) would get
+            order = [train[i] for i in ids]
+            if aug is not None:
+                aug.set_epoch(epoch)
             total, n = torch.zeros(1, dtype=torch.float64, device=dev), 0
-            for x, z, _ in batches_3d(order, a, pool, dev, hpm2d):
+            for x, z, _ in batches_3d(order, a, pool, dev, hpm2d, aug, ids, head_hw * 8):
                 total += trainer.step(x, z, lr=lr) * len(z)
                 n += len(z)
             row = {"epoch": epoch, "lr": lr, "images": n, "loss": float(total / n)}
@@ -266,16 +381,24 @@ def main(argv=None):
         trainer.load_state_dict(hpe_train.init_state_dict(a.init_seed or 0, INIT_WIDTHS))
     out_dir = os.path.join(a.checkpoints_dir, a.name)
     os.makedirs(out_dir, exist_ok=True)
-    rng, log = random.Random(a.seed), []
+    rng, log, aug = random.Random(a.seed), [], Augment.of(a, len(train))
     with ThreadPoolExecutor(a.threads) as pool:
         for epoch in range(1, a.niter + a.niter_decay + 1):
             lr = hpe_train.linear_lr(a.lr, epoch - 1, a.niter, a.niter_decay)
-            order = list(train)
-            rng.shuffle(order)
+            ids = list(range(len(train)))
+            rng.shuffle(ids)                                        # the permutation list(train) would get
+            order = [train[i] for i in ids]
             sums, n = torch.zeros(hpe_train.N_OUT, dtype=torch.float64, device=dev), 0
-            for images, uv in batches(order, a.batchSize, pool, dev):
-                sums += trainer.step(images, uv, layout="bgr_hwc", lr=lr) * images.shape[0]
-                n += images.shape[0]
+            if aug is None:
+                for images, uv in batches(order, a.batchSize, pool, dev):
+                    sums += trainer.step(images, uv, layout="bgr_hwc", lr=lr) * images.shape[0]
+                    n += images.shape[0]
+            else:
+                aug.set_epoch(epoch)
+                for images, uv, which in batches(order, a.batchSize, pool, dev, ids):
+                    x = aug.normalize(images, which)
+                    sums += trainer.step_normalized(x, aug.joints(uv, which, tuple(images.shape[1:3])), lr=lr) * images.shape[0]
+                    n += images.shape[0]
             row = {"epoch": epoch, "lr": lr, "images": n, "loss": (sums / n).tolist()}
             if val is not None:
                 row.update(validate(trainer, val, a, pool, dev))
