@@ -105,6 +105,12 @@ __global__ void __launch_bounds__(64 * (TS / RW), 2) conv_stem16_kernel(const St
     const unsigned x_lane = lds0 + (unsigned)(RW * wave) * (unsigned)p.rp + (unsigned)(l15 * p.C8 + 8 * g4) * 2u;
     const unsigned w_lane = lds0 + (unsigned)p.halo_b + (unsigned)l15 * (unsigned)p.wpitch + (unsigned)(8 * g4) * 2u;
     const unsigned w_nt = 16u * (unsigned)p.wpitch;        // bytes between n tiles
+    // The contraction is padded from ks * C8 to 32 * Jt columns, and a pixel's padded columns lie over the NEXT pixel of the
+    // flat halo row: real data, times weights that are zero - which is 0 only while that data is finite (0 x NaN and
+    // 0 x inf are NaN: a NaN in x came out one pixel to the left of its receptive field, in every channel).  The lanes whose
+    // k slice is padding read the zero-filled tail behind the halo image instead (16 bytes per k slice, within its 256).
+    const int kcut = p.ks * p.C8;
+    const unsigned x_zero = lds0 + (unsigned)(p.hs * p.rp) + 16u * (unsigned)g4;
 
     for (int kh = 0; kh < p.ks; ++kh) {
         __builtin_amdgcn_s_waitcnt(0x0070);                 // this thread's DMA (halo, filter row kh) has landed
@@ -117,7 +123,8 @@ __global__ void __launch_bounds__(64 * (TS / RW), 2) conv_stem16_kernel(const St
 #pragma unroll
             for (int j = 0; j < 4; ++j) wf[j] = lds_frag(wb + (unsigned)j * w_nt + (unsigned)ks * 64u);
 #pragma unroll
-            for (int i = 0; i < RW; ++i) xf[i] = lds_frag(xb + (unsigned)i * (unsigned)p.rp + (unsigned)ks * 64u);
+            for (int i = 0; i < RW; ++i)
+                xf[i] = lds_frag(32 * ks + 8 * g4 >= kcut ? x_zero : xb + (unsigned)i * (unsigned)p.rp + (unsigned)ks * 64u);
 #pragma unroll
             for (int i = 0; i < RW; ++i)
 #pragma unroll

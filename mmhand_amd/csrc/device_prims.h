@@ -56,9 +56,10 @@ __device__ __forceinline__ unsigned lds_addr_of(const void* p) {
     return (unsigned)(size_t)(__attribute__((address_space(3))) const char*)p;
 }
 
-// The epilogue activation of the MMH_ACT_* codes
+// The epilogue activation of the MMH_ACT_* codes.  ReLU lets a NaN through, as torch.relu does (written `v > 0 ? v : 0` it
+// compiled to v_max_f32, which answers 0 for a NaN: an overflow upstream came out of a fused conv + ReLU as a clean zero)
 __device__ __forceinline__ float act_apply(float v, int act) {
-    if (act == MMH_ACT_RELU) return v > 0.f ? v : 0.f;
+    if (act == MMH_ACT_RELU) return v <= 0.f ? 0.f : v;
     if (act == MMH_ACT_TANH) return tanhf(v);
     return v;
 }

@@ -16,6 +16,12 @@ non-zero; bias in {-2 .. 2}; addend within +-8.
 
 The case lists of tests/test_conv_exact_gpu.py live here, so that tests/test_conv_exact_cpu.py checks the caps of every
 (shape, density) pair without a GPU.
+
+What the capped families test, and what they cannot: with every result inside the exact range of its storage type no 16-bit
+store ever rounds, so these families test the SUMS (which products, how often) and say nothing about the STORE.  The
+round-once families at the end of this file lift the caps: operands are integers the 16-bit type still holds exactly, the
+fp32 accumulator still holds the exact sum, and the one correct stored value is the round-to-nearest-even of that sum,
+taken once, after bias and activation (rne16, assert_rounded_once; tests/test_conv_round16_gpu.py and _cpu.py).
 """
 import contextlib
 import functools
@@ -294,3 +300,395 @@ FAMILIES = {
 
 def case_problem(family, case):
     return problem(*FAMILIES[family][1](case))
+
+
+# ================================================================================================ the store: round once
+# The families above keep every result where its storage type is exact.  The families below do the opposite on purpose:
+# operands are integers the 16-bit type holds exactly (|v| <= 256 in bf16, <= 2048 in fp16), optionally times one power of
+# two per operand, so every product and partial sum is still an integer (times that power) below 2^24 and the fp32
+# accumulator holds the exact sum in any order - but the sum no longer fits the 16-bit type.  The one correct stored value
+# is RNE(exact sum + bias, after the activation), bit for bit.  No tolerance anywhere: every expectation is derived.
+TD = {"bf16": torch.bfloat16, "fp16": torch.float16}
+_SIG = {torch.bfloat16: 8, torch.float16: 11}          # significand bits incl. the hidden one
+_EMIN = {torch.bfloat16: -126, torch.float16: -14}     # exponent of the smallest normal
+XMAX = {torch.bfloat16: 256, torch.float16: 2048}      # integers up to here are exact operands
+
+# the conditions on the oracle alone (shares of all elements); a case that misses one gets another xm or density
+MIN_INEXACT, MIN_TIES, MIN_TIES_UP, MIN_TIES_DOWN, MIN_NEG_INEXACT = 0.25, 0.10, 0.04, 0.04, 0.10
+
+
+def _same(a, b):
+    """element-wise a == b with NaN == NaN"""
+    return (a == b) | (a.isnan() & b.isnan())
+
+
+def rne16(t64, td):
+    """round-to-nearest-even of a float64 tensor to bf16 / fp16 (inf on overflow, gradual underflow).  The values must be
+    fp32 values (that is what an accumulator can hold): float64 -> fp32 is then exact and fp32 -> 16 bits rounds once.
+    tests/test_conv_round16_cpu.py checks the cast against integer arithmetic on the fp32 bit pattern."""
+    assert t64.dtype == torch.float64 and td in _SIG, (t64.dtype, td)
+    f = t64.to(torch.float32)
+    assert bool(_same(f.double(), t64).all()), "rne16: a value is not exactly representable in fp32"
+    return f.to(td)
+
+
+def _bits16(t):
+    return t.detach().cpu().contiguous().view(torch.int16).to(torch.int32) & 0xFFFF
+
+
+def assert_bits16(got16, want16, what, exact64=None):
+    """got16 == want16 bit for bit (zeros with their sign); NaN matches NaN whatever the payload"""
+    assert got16.dtype == want16.dtype, (what, got16.dtype, want16.dtype)
+    g, w_ = got16.detach().cpu(), want16.detach().cpu()
+    assert tuple(g.shape) == tuple(w_.shape), (what, tuple(g.shape), tuple(w_.shape))
+    ok = (_bits16(g) == _bits16(w_)) | (g.isnan() & w_.isnan())
+    if bool(ok.all()):
+        return
+    bad = ~ok
+    idx = tuple(int(i) for i in bad.nonzero()[0])
+    ex = "" if exact64 is None else f" (exact value {float(exact64[idx])!r})"
+    raise AssertionError(f"{what}: {int(bad.sum())} of {w_.numel()} elements differ bit for bit; first at index {idx}: got "
+                         f"{float(g[idx])!r} (0x{int(_bits16(g)[idx]):04x}), want {float(w_[idx])!r} (0x{int(_bits16(w_)[idx]):04x}){ex}")
+
+
+def assert_rounded_once(got16, exact64, td, what):
+    """got16 (any device) == RNE(exact64) in td, element by element and bit for bit"""
+    assert got16.dtype == td, (what, got16.dtype, td)
+    assert_bits16(got16, rne16(exact64, td), what, exact64)
+
+
+def round_shares(v64, td):
+    """shares of the elements of v64 that are not representable in td, exact ties, ties that RNE rounds up / down in
+    magnitude, and negative AND not representable - by float64 arithmetic on the value's own 16-bit grid, without a cast"""
+    a = v64.abs()
+    _, e = torch.frexp(a)                                               # a = m 2^e with m in [0.5, 1)
+    e = (e - 1).clamp_min(_EMIN[td])                                    # subnormals share the smallest normal's grid
+    q = a / torch.ldexp(torch.ones_like(a), e - (_SIG[td] - 1))         # in units of the grid: exact (powers of two)
+    fl = q.floor()
+    fr = q - fl
+    tie, odd = fr == 0.5, fl % 2 == 1
+    m = lambda t: float(t.double().mean())     # noqa: E731
+    return dict(inexact=m(fr != 0), ties=m(tie), ties_up=m(tie & odd), ties_down=m(tie & ~odd), neg_inexact=m((fr != 0) & (v64 < 0)))
+
+
+def check_round_conditions(v64, td, what, scale=1.0, relu=False):
+    """the conditions of a round-once problem, on the oracle alone; returns the shares"""
+    assert bool((v64.float().double() == v64).all()), f"{what}: a result is not exactly representable in fp32"
+    assert float(v64.abs().max()) < CAP_F32 * scale, f"{what}: |result| reaches 2^24 x the scale"
+    assert bool(rne16(v64, td).isfinite().all()), f"{what}: a result is not finite in {td} - lower xm"
+    s = round_shares(v64, td)
+    for key, least in (("inexact", MIN_INEXACT), ("ties", MIN_TIES), ("ties_up", MIN_TIES_UP), ("ties_down", MIN_TIES_DOWN)) + \
+            ((("neg_inexact", MIN_NEG_INEXACT),) if relu else ()):
+        assert s[key] >= least, f"{what}: share of {key} elements {s[key]:.3f} < {least} - another xm or density, not a lower share"
+    return s
+
+
+def _xm(nterms, td):
+    """operand magnitude (a power of two, at most what td holds exactly) at which a sum of `nterms` products x * (+-1), x
+    uniform in [-xm, xm] (variance about xm^2 / 3), has a standard deviation of about twice the exact range of td"""
+    import math
+    cap = 2.0 * (CAP_BF16 if td is torch.bfloat16 else CAP_FP16)
+    return int(min(XMAX[td], 2 ** round(math.log2(cap / math.sqrt(nterms / 3.0)))))
+
+
+# round-once families: cases (the shapes the 16-bit families above already have) and spec(case) ->
+# (B, H, W, Cin, Cout, k, stride, pad, reflect, kind, w density, outputs held to the conditions)
+def _r(B, H, W, Cin, Cout, k, s, p, refl, kind="conv", density=W_DENSITY, outs=("y", "dx")):
+    return (B, H, W, Cin, Cout, k, s, p, refl, kind, density, outs)
+
+
+ROUND_FAMILIES = {
+    "halo_fprop": (HALO_FPROP, lambda c: _r(c[0], c[1], c[2], c[3], c[4], 3, 1, 1, c[5], outs=("y",))),
+    "halo_persist_fprop": (HALO_PERSIST_FPROP, lambda c: _r(c[0], c[1], c[2], c[3], c[4], 3, 1, 1, c[5], outs=("y",))),
+    "fold_dgrad": (FOLD_DGRAD, lambda c: _r(c[0], c[1], c[2], c[3], c[4], 3, 1, 1, True, outs=("dx",))),
+    "fold_in_kernel": (FOLD_IN_KERNEL, lambda c: _r(c[0], c[1], c[2], c[3], c[4], 3, 1, 1, True, outs=("dx",))),
+    "halo_persist_dgrad": (HALO_PERSIST_DGRAD, lambda c: _r(*c, 3, 1, 1, True, outs=("dx",))),
+    "lp16g": (LP16G, lambda c: _r(c[0], c[1], c[2], c[3], c[4], 3, c[5], 1, c[6])),
+    "s2_lp16": (S2_LP16, lambda c: _r(c[0], c[1], c[2], c[3], c[4], 3, 2, 1, False)),
+    "s1_lp16": (S1_LP16, lambda c: _r(c[0], c[1], c[2], 64, 64, 3, 1, 1, False)),
+    "flat_stems": (FLAT_STEMS, lambda c: _r(c[0], c[1], c[2], c[3], c[4], c[5], 1, c[5] // 2, c[6], outs=("y",))),
+    "stem16": (STEM16, lambda c: _r(c[0], c[1], c[2], c[3], 64, 7, 1, 3, c[4], density=1.0 if c[3] <= 3 else W_DENSITY, outs=("y",))),
+    "stem16_3x3": (STEM16_3X3, lambda c: _r(c[0], c[1], c[2], c[3], 64, 3, 1, 1, False, density=1.0, outs=("y",))),
+    "head_dgrad": (HEAD_DGRAD, lambda c: _r(c[0], c[1], c[2], 64, 4, 7, 1, 3, True, kind="head", outs=("dx",))),
+    # the same with dense weights: 147 products per element, enough of them to steer an element to the fp16 threshold
+    "head_dgrad_dense": (HEAD_DGRAD[:1], lambda c: _r(c[0], c[1], c[2], 64, 4, 7, 1, 3, True, kind="head", density=1.0, outs=("dx",))),
+    # ConvTranspose2d(k3, s2, p1, op1) of the two LP16G shapes seen from the other side: x [B, H/2, W/2, Cout], w as it is
+    "convT": ([(c[0], c[1] // 2, c[2] // 2, c[4], c[3]) for c in LP16G],
+              lambda c: _r(c[0], c[1], c[2], c[3], c[4], 3, 2, 1, False, kind="convT")),
+}
+
+
+def _nterms(spec):
+    """average number of non-zero products per element of y and of dx"""
+    B, H, W, Cin, Cout, k, stride, pad, reflect, kind, density, outs = spec
+    nz = density * 2.0 / 3.0
+    if kind == "convT":
+        return k * k * Cin / 4.0 * nz, k * k * Cout * nz
+    co = Cout - 1 if kind == "head" else Cout
+    return k * k * Cin * nz, k * k * co / float(stride * stride) * nz
+
+
+def _round_oracle(spec, x, w, bias, dy):
+    """float64 (y before the activation, dx) of the conv that spec describes"""
+    B, H, W, Cin, Cout, k, stride, pad, reflect, kind, density, outs = spec
+    if kind == "convT":
+        y, dx, _, _ = R.convT2d_grads(x, w, bias, dy)
+    else:
+        y, dx, _, _ = R.conv2d_grads(x, w, bias, dy, stride, pad, reflect, 0)
+    return y.detach(), dx.detach()
+
+
+@functools.lru_cache(maxsize=64)
+def round_problem(family, case, lp, edge=None):
+    """One seeded round-once problem and its exact float64 results (shared, read-only!).  lp: "bf16" | "fp16".
+    edge None: integer operands, x in [-xm_x, xm_x], dy in [-xm_dy, xm_dy], w in {-1, 0, 1}, bias in [-2 cap, 2 cap].
+    edge "scaled": the same kind of problem times a power of two per operand - fp16: x, w, dy times 2^-13 with |x|, |dy| <= 8,
+    so that every result is a multiple of 2^-26 below 2^-14 (stored as an fp16 subnormal); bf16: x, w, dy times 2^56, results
+    around 2^120 (the scale is no no-op: one binade lower in the exponent field and everything changes).
+    The conditions (check_round_conditions) are asserted here, on the oracle alone, before anything is compared."""
+    td = TD[lp]
+    spec = ROUND_FAMILIES[family][1](case)
+    B, H, W, Cin, Cout, k, stride, pad, reflect, kind, density, outs = spec
+    ny, ndx = _nterms(spec)
+    xm_x, xm_dy = _xm(ny, td), _xm(ndx, td)
+    bm = int(2 * (CAP_BF16 if td is torch.bfloat16 else CAP_FP16))
+    s_op = 1.0
+    if edge == "scaled":
+        if td is torch.float16:
+            xm_x = xm_dy = 8
+            bm, s_op = 64, 2.0 ** -13
+        else:
+            s_op = 2.0 ** 56
+    else:
+        assert edge is None, edge
+    s_out = s_op * s_op
+    x = ints((B, H, W, Cin), SEED_X, lo=-xm_x, hi=xm_x) * s_op
+    bias = ints((Cout,), SEED_B, lo=-bm, hi=bm) * s_out
+    if kind == "convT":
+        w = ints((3, 3, Cout, Cin), SEED_W, density) * s_op
+        dy = ints((B, 2 * H, 2 * W, Cout), SEED_DY, lo=-xm_dy, hi=xm_dy) * s_op
+    else:
+        w = ints((k, k, Cin, Cout), SEED_W, density) * s_op
+        Ho, Wo = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
+        dy = ints((B, Ho, Wo, Cout), SEED_DY, lo=-xm_dy, hi=xm_dy) * s_op
+        if kind == "head":
+            w[..., -1] = 0; bias[-1] = 0; dy[..., -1] = 0
+    y, dx = _round_oracle(spec, x, w, bias, dy)
+    for name, t in (("x", x), ("w", w), ("dy", dy)):
+        assert torch.equal(t.to(td).float(), t), f"operand {name} is not exact in {td}"
+    what = f"{family} {case} {lp}" + (f" {edge}" if edge else "")
+    shares = {}
+    if "y" in outs:
+        shares["y"] = check_round_conditions(y, td, what + " y", s_out, relu=True)
+        if edge == "scaled" and td is torch.float16:
+            assert float(y.abs().max()) < 2.0 ** -14, what
+    if "dx" in outs:
+        shares["dx"] = check_round_conditions(dx, td, what + " dx", s_out)
+        if edge == "scaled" and td is torch.float16:
+            assert float(dx.abs().max()) < 2.0 ** -14, what
+    return SimpleNamespace(x=x, w=w, bias=bias, dy=dy, y=y, dx=dx, td=td, lp=lp, shares=shares, xm=(xm_x, xm_dy), spec=spec)
+
+
+def round_cases():
+    """every (family, case, lp, edge) the GPU file uses: the main problems of every family in both types, and the scaled
+    edge once per family (its first case)"""
+    out = []
+    for fam, (cases, _) in ROUND_FAMILIES.items():
+        for lp in ("bf16", "fp16"):
+            out += [(fam, c, lp, None) for c in cases]
+            if "persist" not in fam:            # the two large problems run once per type: their epilogues are halo_fprop's
+                out.append((fam, cases[0], lp, "scaled"))
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ fp16 overflow
+# One problem per family whose exact results straddle the fp16 overflow threshold: a few elements of ONE output row are
+# steered, by hand-placed operands, to the values below - six in (65504, 65520), which round to +-65504, and six at or above
+# 65520, which must be +-inf (65520 itself is the tie between 65504 and 2^16: to even, that is to inf).  Every other
+# element stays finite.  Steering is exact: the coefficient of an operand element in a target is a weight (by the oracle on
+# a one-hot, linearity), only operands that reach ONE target are moved, and every operand stays an integer of |v| <= 2048.
+# The case of each family that is steered: its first, except where that one has too few products per element to reach 65520
+# with operands of |v| <= 2048 (the 8-channel flat stem; the sparse head, for which head_dgrad_dense is there).  The 3-channel
+# 3x3 stem form (27 products, at most 55296 + bias) cannot reach it at all: its epilogue is the 7x7 stem's, which is steered.
+OVERFLOW_CASES = {"halo_fprop": HALO_FPROP[0], "fold_dgrad": FOLD_DGRAD[0], "fold_in_kernel": FOLD_IN_KERNEL[0], "lp16g": LP16G[0],
+                  "s2_lp16": S2_LP16[0], "s1_lp16": S1_LP16[0], "flat_stems": FLAT_STEMS[1], "stem16": STEM16[0],
+                  "head_dgrad_dense": HEAD_DGRAD[0], "convT": (1, 16, 10, 256, 128)}
+FP16_MAX, FP16_INF_FROM = 65504.0, 65520.0
+OVERFLOW_TARGETS = (65505.0, 65512.0, 65519.0, -65505.0, -65519.0, 65511.0, 65520.0, 65536.0, -65520.0, 70000.0, -66000.0, 65521.0)
+MIN_EACH_SIDE = 4
+
+
+def _coeffs(spec, w, out, t, xshape, dyshape):
+    """d out[t] / d operand (x for "y", dy for "dx") as a tensor of the operand's shape"""
+    if out == "y":
+        one = torch.zeros(dyshape); one[t] = 1.0
+        return _round_oracle(spec, torch.zeros(xshape), w, None, one)[1]
+    one = torch.zeros(xshape); one[t] = 1.0
+    return _round_oracle(spec, one, w, None, torch.zeros(dyshape))[0]
+
+
+def _steer(opnd, gs, cur, wants, what):
+    """Move the flat integer operand `opnd` (in place, |v| <= 2048 kept) until target j, whose value is cur[j] and whose
+    coefficients are gs[j], equals wants[j] for every j.  Each correction is spread evenly over ALL operands that reach the
+    target with a coefficient of +-1 - the smallest change per operand, so that the elements nobody steers move little and
+    stay finite - and what that does to the other targets (known: the coefficients) is corrected in the next sweep; the
+    last sweeps use only operands that reach one target alone, and end exactly."""
+    cur = list(cur)
+    reach = sum((g != 0).to(torch.int32) for g in gs)
+    for sweep in range(12):
+        if all(c == w_ for c, w_ in zip(cur, wants)):
+            return
+        for j, g in enumerate(gs):
+            rem = wants[j] - cur[j]
+            if rem == 0:
+                continue
+            s = 1.0 if rem > 0 else -1.0
+            cand = ((g.abs() == 1) & ((reach == 1) if sweep >= 4 else (reach >= 1))).nonzero().reshape(-1)
+            gf = g[cand]
+            c = opnd[cand].double() * gf                                # each candidate's contribution to the target now
+            add, left = torch.zeros_like(c), abs(rem)
+            while left > 0:
+                room = 2048.0 - s * c - add
+                free = (room > 0).nonzero().reshape(-1)
+                assert len(free) > 0, f"{what}: target {j} is out of reach (sweep {sweep})"
+                q = float(left // len(free))
+                if q == 0:
+                    add[free[:int(left)]] += 1.0
+                    break
+                inc = torch.minimum(room[free], torch.full_like(room[free], q))
+                add[free] += inc
+                left -= float(inc.sum())
+            step = s * add * gf                                         # the change of the operand itself
+            opnd[cand] = (opnd[cand].double() + step).float()
+            for i, gi in enumerate(gs):
+                cur[i] += float((gi[cand] * step).sum())
+    raise AssertionError(f"{what}: the targets did not converge")
+
+
+@functools.lru_cache(maxsize=16)
+def overflow_problem(family, case):
+    P0 = round_problem(family, case, "fp16")
+    spec = P0.spec
+    x, dy, w, bias = P0.x.clone(), P0.dy.clone(), P0.w, P0.bias
+    targets = {}
+    for out in spec[-1]:
+        res, opnd = (P0.y, x) if out == "y" else (P0.dx, dy)
+        _, Ho, Wo, C = res.shape
+        n = len(OVERFLOW_TARGETS)
+        up = 1 if (spec[6] == 2 and (out == "dx") == (spec[9] != "convT")) else 0      # the up-sampled side of a stride-2 conv: odd
+        ts = [(0, (Ho // 2) | up, ((j * Wo) // n) | up, (7 * j + 3) % C) for j in range(n)]     # coordinates see four taps, not one
+        assert len(set(ts)) == n
+        gs = [_coeffs(spec, w, out, t, x.shape, dy.shape).reshape(-1) for t in ts]
+        _steer(opnd.reshape(-1), gs, [float(res[t]) for t in ts], OVERFLOW_TARGETS, f"overflow_problem {family} {out}")
+        targets[out] = ts
+    y, dx = _round_oracle(spec, x, w, bias, dy)
+    for out, ts in targets.items():
+        res = y if out == "y" else dx
+        for t, want in zip(ts, OVERFLOW_TARGETS):
+            assert float(res[t]) == want, (family, out, t, float(res[t]), want)
+        a = res.abs()
+        n_inf, n_edge = int((a >= FP16_INF_FROM).sum()), int(((a > FP16_MAX) & (a < FP16_INF_FROM)).sum())
+        assert n_edge >= MIN_EACH_SIDE and n_inf >= MIN_EACH_SIDE, (family, out, n_edge, n_inf)
+        assert n_inf == sum(1 for v in OVERFLOW_TARGETS if abs(v) >= FP16_INF_FROM), f"{family} {out}: an element overflows that was not steered"
+        assert bool((res.float().double() == res).all()) and float(a.max()) < CAP_F32
+    for name, t in (("x", x), ("dy", dy)):
+        assert torch.equal(t.to(torch.float16).float(), t), f"operand {name} is not exact in fp16"
+    return SimpleNamespace(x=x, w=w, bias=bias, dy=dy, y=y, dx=dx, td=torch.float16, lp="fp16", spec=spec, targets=targets)
+
+
+# ------------------------------------------------------------------------------------------------ NaN and inf
+@functools.lru_cache(maxsize=32)
+def special_problem(family, case, lp):
+    """The main problem with a NaN in the LAST pixel of the operand (the tail of the last, ragged tile) and +inf in pixel
+    (0, 0, 1).  The oracle propagates both (0 x NaN and 0 x inf are NaN, as in the MFMA); the condition on the oracle: its
+    non-finite elements are exactly those whose receptive field holds one of the two - every channel of those pixels,
+    found by running the same conv on the indicator with all-ones weights."""
+    P0 = round_problem(family, case, lp)
+    spec = P0.spec
+    x, dy, w, bias = P0.x.clone(), P0.dy.clone(), P0.w, P0.bias
+    ind_x, ind_dy = torch.zeros_like(x), torch.zeros_like(dy)
+    for out in spec[-1]:
+        opnd, ind = (x, ind_x) if out == "y" else (dy, ind_dy)
+        c = 0 if spec[9] == "head" else opnd.shape[3] - 1
+        last = (opnd.shape[0] - 1, opnd.shape[1] - 1, opnd.shape[2] - 1, c)
+        opnd[last] = float("nan"); opnd[0, 0, 1, 0] = float("inf")
+        ind[last] = 1.0; ind[0, 0, 1, 0] = 1.0
+    y, dx = _round_oracle(spec, x, w, bias, dy)
+    fy, fdx = _round_oracle(spec, ind_x, torch.ones_like(w), None, ind_dy)
+    for out in spec[-1]:
+        res, field = (y, fy) if out == "y" else (dx, fdx)
+        assert torch.equal(~res.isfinite(), field > 0), f"special_problem {family} {out}: the oracle's non-finite set is not the receptive field"
+        assert 0 < int((field > 0).sum()) < field.numel() // 2
+    return SimpleNamespace(x=x, w=w, bias=bias, dy=dy, y=y, dx=dx, td=TD[lp], lp=lp, spec=spec)
+
+
+# ------------------------------------------------------------------------------------------------ paths that round twice, by design
+def border_sequence(P, td):
+    """mode-1 dgrad of a ReflectionPad2d(1) conv with a 16-bit dx (mmh_conv3x3_lp16 mode 1, then mmh_conv2d_dgrad_border):
+    the halo / row-tile kernel stores RNE(main), main = the zero-padded dgrad; border_add_kernel (conv_igemm.hip) reads that
+    16-bit value at the ring pixels (rows 1, H - 2, columns 1, W - 2), adds the fp32 sum of the border terms - integers,
+    exact in any order - and stores RNE again.  Two roundings at the ring, one elsewhere, in a fixed sequence:
+    dx16 = RNE(RNE(main) + (dx - main)) on the ring, RNE(main) off it; returns (that, the share of elements where it
+    differs from RNE(dx))."""
+    B, H, W, Cin, Cout, k, stride, pad, reflect, kind, density, outs = P.spec
+    main = R.conv2d_grads(P.x, P.w, None, P.dy, 1, 1, False, 0)[1].detach()
+    ring = torch.zeros(main.shape, dtype=torch.bool)
+    ring[:, [1, H - 2], :, :] = True
+    ring[:, :, [1, W - 2], :] = True
+    assert bool(_same(main, P.dx)[~ring].all())                     # the border terms land on the ring and nowhere else
+    once = rne16(main, td)
+    # at a ring pixel the stored value goes through one more fp32 addition (a -0 comes back as +0) and one more rounding;
+    # where main itself is not finite, the stored inf / NaN plus the border terms is what float64 makes of dx = main + border
+    again = torch.where(main.isfinite(), rne16(once.double() + (P.dx - main), td), rne16(P.dx, td))
+    twice = torch.where(ring, again, once)
+    return twice, float((_bits16(twice) != _bits16(rne16(P.dx, td))).double().mean())
+
+
+def head_dgrad_sequence(P, td, dx16):
+    """mmh_conv7_head_dgrad_lp16 (conv_stem16.hip): conv_stem16_kernel stores the gradient over the PADDED domain
+    [B][H + 6][W + 6][64] in 16 bits (RNE, store4); head_dgrad_fold_kernel adds up to nine of those 16-bit values per pixel in
+    fp32 (the transpose of ReflectionPad2d(3); integers, exact in any order) and stores fp32 or, dx_is16, RNE again.
+    dx32 = sum RNE(padded terms); dx16 = RNE(dx32).  dy and w are converted to 16 bits on the way in (exact here or, where a
+    test asks for it, RNE: pass the problem with the rounded operands)."""
+    import torch.nn.functional as F
+    wt = P.w.double().permute(3, 2, 0, 1).contiguous()                                   # [Cout, Cin, kh, kw]
+    dxpad = F.conv_transpose2d(R.to_nchw(P.dy.double()), wt)                             # [B, 64, H + 6, W + 6]
+    dxpad16 = rne16(dxpad, td).double()
+    xz = torch.zeros(P.x.shape[0], P.x.shape[3], P.x.shape[1], P.x.shape[2], dtype=torch.float64, requires_grad=True)
+    (g,) = torch.autograd.grad(F.pad(xz, (3, 3, 3, 3), mode="reflect"), xz, dxpad16)
+    dx32 = R.to_nhwc(g)
+    return rne16(dx32, td) if dx16 else dx32
+
+
+# ------------------------------------------------------------------------------------------------ the conversion kernels' corner table
+def corner_table(td):
+    """One fixed table of fp32 values (built from bit patterns) for the fp32 -> 16-bit conversion kernels: ties to even in both
+    directions at several exponents with the values just either side of each (incl. the tie that carries into the next
+    exponent), the largest finite values, for fp16 65519.99.., 65520 and results that land on subnormals (the 2^-25 tie to
+    zero and its neighbours among them), fp32 subnormals, +-0, +-inf, NaNs.  Starts with (below a tie, the tie, above it),
+    and its length is 6 mod 8: table + table[:2] is a whole number of 8-element vectors whose LAST element is a tie."""
+    import numpy as np
+    drop = 16 if td is torch.bfloat16 else 13              # fp32 mantissa bits the type drops
+    keep = 23 - drop
+    exps = (-126, -60, -1, 0, 1, 7, 64, 127) if td is torch.bfloat16 else (-14, -5, 0, 1, 10, 15)
+    bits = []
+    for e in exps:
+        for hi in (0, 1, (1 << keep) - 2, (1 << keep) - 1):            # kept mantissa even / odd / odd with a carry out of the mantissa
+            tie = ((e + 127) << 23) | (hi << drop) | (1 << (drop - 1))
+            for sign in (0, 0x80000000):
+                bits += [(tie - 1) | sign, tie | sign, (tie + 1) | sign]
+    if td is torch.float16:
+        bits += [0x477FE000, 0x477FEFFF, 0x477FF000, 0x477FF001, 0x47800000, 0xC77FEFFF, 0xC77FF000]      # 65504, 65519.99.., 65520 ..
+        for k in (0, 1, 2, 5, 511, 1022, 1023):                                                              # (k + 1/2) 2^-24: subnormal ties
+            v = np.float32((k + 0.5) * 2.0 ** -24)
+            for f in (np.nextafter(v, np.float32(0)), v, np.nextafter(v, np.float32(1))):
+                b = int(np.float32(f).view(np.uint32))
+                bits += [b, b | 0x80000000]
+        bits += [0x33800000, 0x33000000 - (1 << 23), 0x387FC000]                                            # 2^-24, 2^-26, the largest subnormal
+    else:
+        bits += [0x7F7F0000, 0x7F7F7FFF, 0x7F7F8000, 0x7F7FFFFF, 0xFF7F8000]                              # around the largest finite bf16
+        bits += [0x00008000, 0x00007FFF, 0x00008001, 0x00018000, 0x00010000, 0x80008000]                  # bf16 subnormals and their ties
+    bits += [0x00000001, 0x007FFFFF, 0x80000001, 0x00000000, 0x80000000, 0x7F800000, 0xFF800000, 0x7FC00000, 0xFFC00001, 0x7F800001]
+    while len(bits) % 8 != 6:
+        bits.append(0x80000000 if len(bits) % 2 else 0)
+    return torch.from_numpy(np.array(bits, dtype=np.uint32).view(np.float32).copy())

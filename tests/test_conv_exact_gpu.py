@@ -10,6 +10,9 @@ One parametrised test per kernel family, through the wrapper the family's rel-L1
 intended kernel ran, at the smallest ragged shapes the family already has.  The cases live in tests/_exact.py; the caps
 (results integer-valued and within the exact range of the type that stores them) are asserted inside E.case_problem on the
 oracle alone, before anything is compared, and again without a GPU by tests/test_conv_exact_cpu.py.
+These capped families test the SUMS: with every result inside the exact range of its storage type no 16-bit store here ever
+rounds, so a kernel that truncates, rounds twice or saturates passes this file.  The STORE is tested by the round-once families
+of tests/_exact.py in tests/test_conv_round16_gpu.py (results that do not fit the 16-bit type, held to RNE bit for bit).
 Statistics by-products of epilogues are not integer quantities: only conv outputs are compared here.
 The templates, work partitions and mmh_set_option knobs that only larger shapes select are in tests/test_conv_variants_gpu.py."""
 import ctypes
