@@ -1243,6 +1243,36 @@ size_t mmh_poly_mmd_sums_ws_bytes(int S, int Ma, int Mb);
 int mmh_poly_mmd_sums(const float* A, const float* B, int d, const int32_t* idxA /* [S][Ma] */, const int32_t* idxB /* [S][Mb] */,
                       int S, int Ma, int Mb, double* out /* [S][3] */, void* ws, mmh_stream_t s);
 
+/* ---- LPIPS, the learned perceptual distance (mmhand_amd/lpips.py; csrc/lpips.hip).  The reference has no such metric; the
+ *      definition is the `lpips` package's LPIPS(net="vgg", spatial=False) in eval mode (lpips/lpips.py, lpips/
+ *      pretrained_networks.py: vgg16).  The VGG-16 trunk is mmh_conv2d_fprop (zero padding, ReLU) and mmh_maxpool2x2_fwd.
+ *
+ * mmh_lpips_preprocess replaces lpips.py's ScalingLayer (and, for bytes, the package's im2tensor): src = B images [3][H][W] of
+ *   any mmh_image_src dtype and strides (scale / offset are not looked at).  v = the stored value for fp32 / bf16 / fp16 - an
+ *   image in [-1, 1] as the generator leaves it -, v = u / 255 * 2 - 1 for MMH_U8.  out [B][H][W][4] fp32: lane c < 3 =
+ *   (float)((v_c - shift_c) / scale_c), shift = (-.030, -.088, -.188), scale = (.458, .448, .450), each constant the float32
+ *   value of its literal widened to float64; float64 arithmetic without fused multiply-add, one rounding; lane 3 zero.
+ *   out 16-byte aligned.
+ * mmh_lpips_layer replaces, for one tap, lpips.normalize_tensor of both feature maps, the squared difference, the NetLinLayer
+ *   (a 1x1 convolution [1,C,1,1] without bias) and spatial_average (lpips.py:9-10,28-30,88-115).  fa, fb: contiguous fp32
+ *   [B][H][W][C]; w: fp32 [C] (any sign; all ones = the package's lpips=False form); out: float64 [B].  In float64, per pixel p:
+ *     n_a = sqrt(sum_c a_c^2), ah_c = a_c / (n_a + 1e-10), likewise b;  d(p) = sum_c w_c (ah_c - bh_c)^2;
+ *     out[b] = (sum_p d(p)) / (H W).
+ *   Both maps are read once, 16 bytes per lane and load, several lanes per pixel; the three sums over c are cross-lane
+ *   butterflies, a and b through one sequence of operations: mmh_lpips_layer(a, b) == mmh_lpips_layer(b, a) bit for bit.  A
+ *   pixel whose vector is all zero contributes through the 1e-10 alone (0 / 1e-10 = 0) and stays finite.  Workgroup k of an
+ *   image (at most 1024 of them) sums its pixels and writes one double to the workspace; a finishing launch adds an image's
+ *   partials in a fixed order (thread t: t, t + 256, ...; then a tree) and divides once.  The launch shape follows from
+ *   (H W, C) alone and the grid is (workgroups, B): out[b] does not depend on B or on the other images, and is bit-identical
+ *   run to run.  No atomics.
+ *   C % 4 == 0, 4 <= C <= 512, 1 <= B <= 65535, H, W >= 1, B H W C < 2^31.  fa, fb, w 16-byte, out and ws 8-byte aligned.
+ *   ws: mmh_lpips_layer_ws_bytes(B, H, W, C) bytes (0 = the shape is refused) = 8 B (workgroups per image).
+ * Bad arguments (NULL, a refused shape, a short workspace, misalignment) return non-zero before any launch.                  */
+int mmh_lpips_preprocess(const mmh_image_src* src, int B, int H, int W, float* out, mmh_stream_t s);
+size_t mmh_lpips_layer_ws_bytes(int B, int H, int W, int C);
+int mmh_lpips_layer(const float* fa, const float* fb, const float* w, int B, int H, int W, int C, double* out /* [B] */, void* ws,
+                    size_t ws_bytes, mmh_stream_t s);
+
 /* replaces inception.py:168 (F.adaptive_avg_pool2d(x, (1, 1))): x fp32 [B][H][W] pixels of C lanes with pixel stride x_cs ->
  * y fp32 [B][C] = (float)(sum / (H W)), the sum taken in float64 over the pixels in order.  One thread per value, no atomics. */
 int mmh_global_avgpool(const float* x, int B, int H, int W, int C, int x_cs, float* y, mmh_stream_t s);

@@ -65,7 +65,22 @@ says so: KID is the figure to read.  Without `--fid` nothing of it is imported o
 
 Two-directory mode - any two sets of PNGs, no labels; this scores `aug --novel` output against real images:
 
-    python -m mmhand_amd.evaluate --fid_images DIR --fid_real DIR|stats.npz --fid <pth> [--fid_variant V] [--batchSize 16] ..."""
+    python -m mmhand_amd.evaluate --fid_images DIR --fid_real DIR|stats.npz --fid <pth> [--fid_variant V] [--batchSize 16] ...
+
+`--lpips <pth> --lpips_lin <pth>|uniform`: also LPIPS, the learned perceptual distance (the `lpips` package's LPIPS(net="vgg");
+mmhand_amd/lpips.py) of every scored image against its target: both go through a VGG-16 trunk on the device and the five
+taps' normalised, weighted squared differences are averaged there - `LPIPS_avg`, `LPIPS_layers` (the five taps' means) and
+`lpips_lin` in the summary, a `lpips` column in the per-image CSV.  <pth> is torchvision's VGG-16 state dict; --lpips_lin names
+the package's linear heads (weights/v0.1/vgg.pth) or `uniform` for the unweighted form (the package's lpips=False).  The image
+size must be a multiple of 16.  Under --resize_inputs N the target is the decode pass's N x N image, as for SSIM.  AlexNet-LPIPS
+is not offered (its stride-4 convolution has no kernel here).  Without `--lpips` nothing of it is imported or launched and the
+files are what they were.
+
+Two-directory mode - two directories of PNGs paired by relative file name, no labels; an unpaired file is an error:
+
+    python -m mmhand_amd.evaluate --lpips_images DIR --lpips_ref DIR --lpips <pth> --lpips_lin <pth>|uniform [--batchSize 16] ...
+
+No VGG-16 or LPIPS weights ship with this repository or the reference: a distance means what its files mean."""
 import argparse
 import csv
 import json
@@ -91,6 +106,7 @@ def build_parser():
     src.add_argument("--pck_images", help="prepared directory whose colour images are scored against its own labels: PCK only")
     src.add_argument("--is_images", help="directory whose PNGs (at any depth) get an Inception score: no labels, IS only")
     src.add_argument("--fid_images", help="directory whose PNGs (at any depth) are scored against --fid_real: FID / KID only")
+    src.add_argument("--lpips_images", help="directory whose PNGs are scored against the same names below --lpips_ref: LPIPS only")
     p.add_argument("--checkpoints_dir", default="checkpoints")
     p.add_argument("--which_epoch", default="latest")
     p.add_argument("--dataroot", default=None, help="prepared RHD / STB directory (annotation.pickle + PNGs); required except "
@@ -132,6 +148,10 @@ def build_parser():
     p.add_argument("--kid_subsets", type=int, default=100, help="with --fid: number of random subsets of KID (torch-fidelity's 100)")
     p.add_argument("--kid_subset_size", type=int, default=1000, help="with --fid: images per subset, clamped to the smaller set")
     p.add_argument("--kid_seed", type=int, default=0, help="with --fid: seed of the subsets' np.random.RandomState")
+    p.add_argument("--lpips", default=None, help="also LPIPS (VGG-16) against the target: torchvision's vgg16 state dict")
+    p.add_argument("--lpips_lin", default=None, help="with --lpips: the lpips package's linear heads (lin{0..4}.model.1.weight), "
+                                                     "or 'uniform' for the unweighted form; required with --lpips")
+    p.add_argument("--lpips_ref", default=None, help="with --lpips_images: the directory of the reference PNGs, same relative names")
     return p
 
 
@@ -283,11 +303,94 @@ def _main_fid_images(args):
     out = args.results_json or os.path.join(args.fid_images, "eval_fid.json")
     os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
     with open(out, "w") as fh:
-        json.dump({"summary": summary, "options": {k: v for k, v in vars(args).items() if k not in IS_FLAGS + PCK_FLAGS},
+        json.dump({"summary": summary, "options": {k: v for k, v in vars(args).items() if k not in IS_FLAGS + PCK_FLAGS + LPIPS_FLAGS},
                    "generator": None,
                    "domain": "the PNGs' bytes, resized to 299 as PIL.Image.resize(BILINEAR), centre crop, the variant's normalisation"},
                   fh, indent=1)
     return {"summary": summary, "rows": []}
+
+
+LPIPS_FLAGS = ("lpips", "lpips_lin", "lpips_images", "lpips_ref")
+LPIPS_KEYS = ("LPIPS_avg", "LPIPS_layers", "lpips_lin")
+
+
+def _lpips_scorer(args, dev):
+    """the LPIPS scorer of --lpips, or None (then nothing of it is imported, loaded or launched)"""
+    if not getattr(args, "lpips", None):
+        return None
+    from .lpips import LpipsScorer
+    return LpipsScorer(args.lpips, args.lpips_lin, device=dev)
+
+
+def _lpips_summary(lsc, summary, rows):
+    """the scorer's figures into the summary, a lpips value into the rows"""
+    res = lsc.results()
+    for k in LPIPS_KEYS:
+        summary[k] = res[k]
+    own = lsc.rows()
+    if rows is None:
+        return own
+    assert len(rows) == len(own)
+    for r, e in zip(rows, own):
+        assert r.get("target") == e.get("target"), (r, e)
+        r["lpips"] = e["lpips"]
+    return rows
+
+
+def _main_lpips_images(args):
+    """--lpips_images DIR --lpips_ref DIR: two directories of PNGs paired by relative file name, no labels"""
+    from .data import _read_bgr
+
+    def listing(root, flag):
+        if not os.path.isdir(root):
+            raise SystemExit(f"evaluate: {flag} {root} is not a directory")
+        names = sorted(os.path.relpath(os.path.join(d, f), root) for d, _, fs in os.walk(root) for f in fs
+                       if f.lower().endswith(".png"))
+        if not names:
+            raise SystemExit(f"evaluate: {flag} {root} holds no PNG")
+        return names
+
+    names, ref = listing(args.lpips_images, "--lpips_images"), listing(args.lpips_ref, "--lpips_ref")
+    if names != ref:
+        odd = sorted(set(names) ^ set(ref))
+        raise SystemExit(f"evaluate: --lpips_images / --lpips_ref: {len(odd)} file(s) without a partner of the same relative name, "
+                         f"e.g. {odd[0]}")
+    torch.cuda.set_device(args.gpu)
+    dev = torch.device("cuda", args.gpu)
+    lsc = _lpips_scorer(args, dev)
+    batch = []
+
+    def flush():
+        if batch:
+            lsc.feed(torch.from_numpy(np.stack([a for _, a, _ in batch])).to(dev), "bgr_hwc",
+                     torch.from_numpy(np.stack([b for _, _, b in batch])).to(dev), "bgr_hwc", [{"target": n} for n, _, _ in batch])
+            batch.clear()
+
+    for n in names:
+        a, b = _read_bgr(os.path.join(args.lpips_images, n)), _read_bgr(os.path.join(args.lpips_ref, n))
+        if a.shape != b.shape:
+            raise SystemExit(f"evaluate: {n}: {a.shape} below --lpips_images, {b.shape} below --lpips_ref")
+        if batch and (len(batch) == args.batchSize or batch[0][1].shape != a.shape):
+            flush()
+        batch.append((n, a, b))
+    flush()
+    summary = {"n": len(names)}
+    rows = _lpips_summary(lsc, summary, None)
+    print(json.dumps(summary))
+    out = args.results_json or os.path.join(args.lpips_images, "eval_lpips.json")
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, "w") as fh:
+        json.dump({"summary": summary,
+                   "options": {k: v for k, v in vars(args).items() if k not in IS_FLAGS + PCK_FLAGS + FID_FLAGS},
+                   "generator": None, "domain": "the PNGs' bytes as RGB in [-1, 1]: u / 255 * 2 - 1, then the LPIPS scaling layer"},
+                  fh, indent=1)
+    if args.per_image_csv:
+        with open(args.per_image_csv, "w", newline="") as fh:
+            w = csv.writer(fh)
+            w.writerow(["target", "lpips"])
+            for r in rows:
+                w.writerow([r["target"], repr(r["lpips"])])
+    return {"summary": summary, "rows": rows}
 
 
 def _pose_labels(loader, paths, size=None):
@@ -310,7 +413,7 @@ def _score_generator(args, ckpt, dev):
     from .inference import InferenceGenerator
     from .networks import Generator
     est, isc = _estimator(args, dev), _scorer(args, dev)
-    fsc = _fid_scorer(args, dev, isc)
+    fsc, lsc = _fid_scorer(args, dev, isc), _lpips_scorer(args, dev)
     sd = strip_module(torch.load(ckpt, map_location="cpu"))
     ngf, n_blocks, norm, use_dropout = infer_generator_config(sd)
     net = Generator(input_nc=[3, 42, 6], output_nc=3, ngf=ngf, norm_layer=norm, use_dropout=use_dropout, n_blocks=n_blocks)
@@ -329,8 +432,10 @@ def _score_generator(args, ckpt, dev):
             _feed_scorers(isc, fsc, fake, "nchw", paths, s["H2"], "nchw")
         elif isc is not None:   # likewise: the scorer's first kernel turns the tensor into the bytes aug would write
             isc.feed(fake, "nchw", paths)
+        if lsc is not None:     # LPIPS: the fake batch against the target the SSIM meter scores it against
+            lsc.feed(fake, "nchw", s["H2"], "nchw", paths)
     return (meter, {"ngf": ngf, "n_blocks": n_blocks, "norm": norm, "use_dropout": use_dropout}, _pose_distances(args, loader),
-            est, isc, fsc)
+            est, isc, fsc, lsc)
 
 
 def _read_generated(path):
@@ -360,7 +465,7 @@ def _score_directory(args, dev):
     # PNGs' bytes are mapped to the same [-1, 1] range
     meter = QualityMeter("pm1" if size else "u8_bgr_hwc", args.window)
     est, isc = _estimator(args, dev), _scorer(args, dev)
-    fsc = _fid_scorer(args, dev, isc)
+    fsc, lsc = _fid_scorer(args, dev, isc), _lpips_scorer(args, dev)
     idx = loader.indices()
     for i in range(0, len(idx), args.batchSize):
         tgts = [loader.image_target[j] for j in idx[i:i + args.batchSize]]
@@ -384,6 +489,10 @@ def _score_directory(args, dev):
             _feed_scorers(isc, fsc, g8, "bgr_hwc", [{"target": t, "source": s} for t, s in zip(tgts, srcs)], real, real_layout)
         elif isc is not None:
             isc.feed(g8, "bgr_hwc", [{"target": t, "source": s} for t, s in zip(tgts, srcs)])
+        if lsc is not None:     # LPIPS: the PNGs' bytes against what the SSIM meter below takes as the target
+            r8 = torch.from_numpy(np.stack(ref)).to(dev).contiguous()
+            tgt, tgt_layout = (_targets_at(r8, size), "nchw") if size else (r8, "bgr_hwc")
+            lsc.feed(g8, "bgr_hwc", tgt, tgt_layout, [{"target": t, "source": s} for t, s in zip(tgts, srcs)])
         if size:
             pred = (g8.flip(-1).permute(0, 3, 1, 2).float() / 255.0 - 0.5) / 0.5
             meter.feed(pred, _targets_at(torch.from_numpy(np.stack(ref)).to(dev).contiguous(), size),
@@ -391,7 +500,7 @@ def _score_directory(args, dev):
             continue
         meter.feed(g8, torch.from_numpy(np.stack(ref)).to(dev),
                    [{"target": t, "source": s} for t, s in zip(tgts, srcs)])
-    return meter, {}, _pose_distances(args, loader), est, isc, fsc
+    return meter, {}, _pose_distances(args, loader), est, isc, fsc, lsc
 
 
 def _is_summary(isc, summary, rows):
@@ -438,7 +547,7 @@ def _main_is_images(args):
     out = args.results_json or os.path.join(args.is_images, "eval_is.json")
     os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
     with open(out, "w") as fh:
-        json.dump({"summary": summary, "options": {k: v for k, v in vars(args).items() if k not in FID_FLAGS}, "generator": None,
+        json.dump({"summary": summary, "options": {k: v for k, v in vars(args).items() if k not in FID_FLAGS + LPIPS_FLAGS}, "generator": None,
                    "domain": "the PNGs' bytes, resized to 299 as PIL.Image.resize(BILINEAR), centre crop, ImageNet normalisation"},
                   fh, indent=1)
     if args.per_image_csv:
@@ -501,7 +610,7 @@ def _main_pck_images(args):
     out = args.results_json or os.path.join(args.pck_images, f"eval_pck_{args.dataset}.json")
     os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
     with open(out, "w") as fh:
-        json.dump({"summary": summary, "options": {k: v for k, v in vars(args).items() if k not in IS_FLAGS + FID_FLAGS}, "generator": None,
+        json.dump({"summary": summary, "options": {k: v for k, v in vars(args).items() if k not in IS_FLAGS + FID_FLAGS + LPIPS_FLAGS}, "generator": None,
                    "domain": "min-max normalised per image, as the reference's datasets hand real images to the estimators"},
                   fh, indent=1)
     if args.per_image_csv:
@@ -541,10 +650,22 @@ def main(argv=None):
         parser.error("--fid scores generated images against real ones: not with --is_images / --pck_images (see --fid_images)")
     if args.fid and (args.kid_subsets < 1 or args.kid_subset_size < 2):
         parser.error("--kid_subsets must be >= 1 and --kid_subset_size >= 2")
+    if args.lpips and not args.lpips_lin:
+        parser.error("--lpips needs --lpips_lin <the lpips package's linear heads | uniform>")
+    if args.lpips_images and not (args.lpips and args.lpips_ref):
+        parser.error("--lpips_images needs --lpips <VGG-16 state dict>, --lpips_lin <file | uniform> and --lpips_ref <directory>")
+    if not args.lpips and args.lpips_lin:
+        parser.error("--lpips_lin needs --lpips <VGG-16 state dict>")
+    if args.lpips_ref and not args.lpips_images:
+        parser.error("--lpips_ref belongs to --lpips_images")
+    if args.lpips and (args.is_images or args.pck_images or args.fid_images):
+        parser.error("--lpips scores image pairs: not with --is_images / --pck_images / --fid_images (see --lpips_images)")
     if args.is_images:
         return _main_is_images(args)
     if args.fid_images:
         return _main_fid_images(args)
+    if args.lpips_images:
+        return _main_lpips_images(args)
     if not args.dataset:
         parser.error("the following arguments are required: --dataset")
     if args.pck_images:
@@ -560,7 +681,7 @@ def main(argv=None):
         raise SystemExit(f"evaluate: --generated {args.generated} is not a directory")
     torch.cuda.set_device(args.gpu)
     dev = torch.device("cuda", args.gpu)
-    meter, config, pose_d, est, isc, fsc = _score_generator(args, ckpt, dev) if ckpt else _score_directory(args, dev)
+    meter, config, pose_d, est, isc, fsc, lsc = _score_generator(args, ckpt, dev) if ckpt else _score_directory(args, dev)
     res = meter.result()
     summary = res["summary"]
     pck_cols = _pck_summary(args, est, summary, res["rows"])[1] if est is not None else []
@@ -569,6 +690,9 @@ def main(argv=None):
         pck_cols = pck_cols + ["is_kl"]
     if fsc is not None:
         _fid_summary(args, fsc, summary)
+    if lsc is not None:
+        _lpips_summary(lsc, summary, res["rows"])
+        pck_cols = pck_cols + ["lpips"]
     if pose_d is not None:
         for r in res["rows"]:
             r["pose_distance"] = pose_d[(r["target"], r["source"])]
@@ -590,6 +714,8 @@ def main(argv=None):
             options = {k: v for k, v in options.items() if k not in IS_FLAGS}
         if fsc is None:                         # and FID / KID's: only under --fid
             options = {k: v for k, v in options.items() if k not in FID_FLAGS}
+        if lsc is None:                         # and LPIPS's: only under --lpips
+            options = {k: v for k, v in options.items() if k not in LPIPS_FLAGS}
         json.dump({"summary": summary, "options": options, "generator": config or None,
                    "domain": "[0, 1]: generator output (x + 1) / 2, PNG pixels u8 / 255"}, fh, indent=1)
     if args.per_image_csv:

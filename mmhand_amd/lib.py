@@ -241,6 +241,9 @@ SIGNATURES = {
     "mmh_feature_moments": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp]),
     "mmh_poly_mmd_sums_ws_bytes": (_sz, [_i, _i, _i]),
     "mmh_poly_mmd_sums": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    "mmh_lpips_preprocess": (_i, [C.POINTER(ImageSrc), _i, _i, _i, _vp, _vp]),
+    "mmh_lpips_layer_ws_bytes": (_sz, [_i, _i, _i, _i]),
+    "mmh_lpips_layer": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "mmh_heatmap_mse_ws_bytes": (_sz, [_i, _i, _i, _i]),
     "mmh_heatmap_mse": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _d, _vp, _vp, _vp, _i, _vp, _sz, _vp]),
     "mmh_lane_add": (_i, [_vp, _i, _vp, _i, _i64, _i, _vp]),

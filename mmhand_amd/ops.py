@@ -3823,3 +3823,40 @@ def poly_mmd_sums(A, B, idxA, idxB):
     out = torch.empty((S, 3), dtype=torch.float64, device=A.device)
     L.call("mmh_poly_mmd_sums", _ptr(A), _ptr(B), d, _ptr(da), _ptr(db), S, Ma, Mb, _ptr(out), _ptr(ws), _stream())
     return out
+
+
+# ----------------------------------------------------------------------------- LPIPS passes (csrc/lpips.hip)
+def lpips_preprocess(images, layout):
+    """lpips.py's ScalingLayer for a batch -> the VGG-16 trunk's input, fp32 [B,H,W,4] with lane 3 zero.  images / layout as
+    _image_src: fp32 / bf16 / fp16 values are taken as an image in [-1, 1] (a generator's output), uint8 values u become
+    u / 255 * 2 - 1; then (v - shift) / scale per channel in float64, one rounding (mmh_lpips_preprocess)."""
+    src, B, H, W_ = _image_src(images, layout, "lpips_preprocess")
+    out = torch.empty((B, H, W_, 4), dtype=torch.float32, device=images.device)
+    L.call("mmh_lpips_preprocess", C.byref(src), B, H, W_, _ptr(out), _stream())
+    return out
+
+
+def lpips_layer(fa, fb, w, out=None, ws=None):
+    """fa, fb fp32 [B,H,W,C] (C % 4 == 0, 4 <= C <= 512), w fp32 [C] -> float64 [B] on the device: per image the mean over the
+    pixels of sum_c w_c (a_c / (|a| + 1e-10) - b_c / (|b| + 1e-10))^2, float64 throughout, both maps read once
+    (mmh_lpips_layer).  Bit-identical run to run, independent of the batch, and the same bits for (fb, fa).  out: a contiguous
+    float64 [B] view to write into; ws: a float64 workspace of at least mmh_lpips_layer_ws_bytes (new tensors if None)."""
+    for t, name in ((fa, "fa"), (fb, "fb"), (w, "w")):
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+            raise ValueError(f"lpips_layer: {name} must be a contiguous fp32 CUDA tensor")
+    if fa.dim() != 4 or fa.shape != fb.shape or fa.device != fb.device or w.device != fa.device:
+        raise ValueError(f"lpips_layer: fa {tuple(fa.shape)} and fb {tuple(fb.shape)}: one [B,H,W,C] shape, one device")
+    B, H, W_, c = fa.shape
+    if tuple(w.shape) != (c,):
+        raise ValueError(f"lpips_layer: w {tuple(w.shape)} for C = {c}")
+    nbytes = L.load().mmh_lpips_layer_ws_bytes(B, H, W_, c)
+    if nbytes == 0:
+        raise ValueError(f"lpips_layer: shape {tuple(fa.shape)} refused (C a multiple of 4 from 4 to 512, fewer than 2^31 elements)")
+    out = torch.empty((B,), dtype=torch.float64, device=fa.device) if out is None else out
+    ws = torch.empty((nbytes // 8,), dtype=torch.float64, device=fa.device) if ws is None else ws
+    for t, shape, name in ((out, (B,), "out"), (ws, None, "ws")):
+        if not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and t.device == fa.device and
+                (shape is None or tuple(t.shape) == shape)):
+            raise ValueError(f"lpips_layer: {name} must be a contiguous float64 CUDA tensor" + (f" {shape}" if shape else ""))
+    L.call("mmh_lpips_layer", _ptr(fa), _ptr(fb), _ptr(w), B, H, W_, c, _ptr(out), _ptr(ws), ws.numel() * 8, _stream())
+    return out
