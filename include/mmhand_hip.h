@@ -990,6 +990,47 @@ int mmh_image_metrics(const mmh_image_src* a, const mmh_image_src* b, int B, int
                       double c1, double c2, void* ws, size_t ws_bytes, double* out /* [B][3]: ssim, l1, mse */,
                       mmh_stream_t s);
 
+/* ---- the same pass with a region mask (evaluate --hand_region): mmh_image_metrics plus the three means over a mask's pixels ----
+ * a, b, B .. c2 as mmh_image_metrics (window 3 .. 15, caller-passed fp32 taps, the four storage types, any strides).
+ * mask: uint8 [B][H][W], element (b, y, x) at mask + b msb + y msh + x msw (bytes); non-zero = inside; one mask serves all C
+ * channels of its image.  One pass writes, float64,
+ *   out[b][0..2] = ssim, l1, mse of the whole image, bit-identical to mmh_image_metrics on the same inputs;
+ *   out[b][3..5] = the same zero-padded ssim_map (computed from the unmasked images), |a-b| and (a-b)^2 averaged over the mask's
+ *                  pixels and the C channels: sum * (1.0 / ((double)C * count)), the float64 sums taken in the same fixed order as
+ *                  the whole-image sums (a pixel outside the mask contributes 0.0 in its place), so an all-ones mask returns the
+ *                  whole-image bits; NaN where count = 0;
+ *   out[b][6]    = count, the number of non-zero mask bytes of image b.
+ * No atomics: an image's result is bit-identical run to run and does not depend on the batch; f(a, b) == f(b, a) bit for bit.
+ * ws: mmh_image_metrics_masked_ws_bytes(B, C, H, W, window) bytes (0 = the arguments are refused).                            */
+size_t mmh_image_metrics_masked_ws_bytes(int B, int C, int H, int W, int window);
+int mmh_image_metrics_masked(const mmh_image_src* a, const mmh_image_src* b, const uint8_t* mask, int64_t msb, int64_t msh,
+                             int64_t msw, int B, int C, int H, int W, int window, const float* taps, double c1, double c2, void* ws,
+                             size_t ws_bytes, double* out /* [B][7] */, mmh_stream_t s);
+
+/* ---- multi-scale SSIM (Wang, Simoncelli, Bovik 2003) from the same tile pass (evaluate --ms_ssim) -------------------------------
+ * a, b, B .. c2 as mmh_image_metrics.  levels L in 1 .. 5; weights: host memory, L doubles, each finite and > 0.
+ * Level 0 is the pair mapped to [0, 1]; level l + 1 is level l averaged 2 x 2 in fp32: pooled pixel (i, j) =
+ * ((v00 + v01) + (v10 + v11)) * 0.25f, evaluated as written, over rows 2 i - ph, 2 i - ph + 1 and columns 2 j - pw, 2 j - pw + 1
+ * with ph = H_l % 2, pw = W_l % 2; values outside the image are zero and the divisor is always 4 - torch's
+ * F.avg_pool2d(x, 2, padding=(H % 2, W % 2)); H_{l+1} = (H_l + 1) / 2 (integer division), likewise W.  The workgroup that scores
+ * a tile of level l writes its part of level l + 1 from the halo it holds (the pyramid lies in the workspace; no separate pooling
+ * pass reads a level).
+ * At level l only the output pixels whose whole window lies inside the image count: window / 2 <= y < H_l - window / 2, likewise
+ * x - count_l = (H_l - window + 1)(W_l - window + 1) - where the zero-padded ssim_map of mmh_image_metrics equals a "valid"
+ * convolution.  With s_a^2, s_b^2, s_ab of that map, cs = (2 s_ab + c2) / ((s_a^2 + s_b^2) + c2), written like the ssim
+ * expression without contraction in mirror-image form: cs(x, x) == 1 and cs(a, b) == cs(b, a) bitwise.
+ * Per image b and channel c, v_l = (fixed-order float64 sum over the counted pixels) * (1.0 / count_l) of cs for l < L - 1 and of
+ * ssim_map for l = L - 1;  scales[b][c][l] = v_l (unclamped);  out[b] = (sum over c of prod over l of pow(max(v_l, 0),
+ * weights[l])) / C, float64.  Each v_l is within 1e-6 of the float64 formula on the fp32-pooled level.  No atomics: bit-identical
+ * run to run, independent of the batch, symmetric in (a, b) bit for bit, 1.0 for a == b.
+ * Refused (ws_bytes 0, non-zero return before any launch): the shape limits of mmh_image_metrics, levels outside 1 .. 5, and
+ * min(H, W) <= (window - 1) * 2^(L - 1) (at L = 5 and window 11: min side > 160; the last level then holds a whole window).
+ * ws: mmh_ms_ssim_ws_bytes(B, C, H, W, window, levels) bytes, 8-byte aligned.                                                  */
+size_t mmh_ms_ssim_ws_bytes(int B, int C, int H, int W, int window, int levels);
+int mmh_ms_ssim(const mmh_image_src* a, const mmh_image_src* b, int B, int C, int H, int W, int window, const float* taps, double c1,
+                double c2, int levels, const double* weights, void* ws, size_t ws_bytes, double* scales /* [B][C][levels] */,
+                double* out /* [B] */, mmh_stream_t s);
+
 /* ---- PNG decode of a batch on the device (data/generic_dataset.py:140-149: the four cv2.imread calls per sample) ----------
  * N zlib streams - each the concatenated IDAT payload of ONE 8-bit, colour type 2 (RGB), non-interlaced PNG of H x W pixels,
  * which is what cv2.imwrite and PIL write for the prepared RHD / STB directories - are inflated (RFC 1950 / 1951: stored, fixed

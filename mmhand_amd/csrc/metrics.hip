@@ -26,7 +26,9 @@
 //
 // Symmetry: the a and b paths are the same instructions, and the cross terms and the combination are written without
 // contraction in mirror-image form, so ssim(a, b) == ssim(b, a) bit for bit and ssim(x, x) == 1 exactly.
+#include <algorithm>
 #include <cmath>
+#include <type_traits>
 #include "common.h"
 
 namespace {
@@ -95,9 +97,14 @@ __device__ __forceinline__ void load_halos(const mmh_image_src& A, int64_t baseA
     }
 }
 
-// SSIM of one pixel from its moments about (ca, cb) (m = a', b', a'^2, b'^2, a'b').  No contraction: every expression is
-// evaluated as written, the a and b operands in mirror-image positions.
-__device__ __forceinline__ float ssim_px(const float* m, float ca, float cb, const MetricTaps& t) {
+// The four factors of one pixel's SSIM from its moments about (ca, cb) (m = a', b', a'^2, b'^2, a'b'): luminance ln / ld,
+// contrast-structure cn / cd.  No contraction: every expression is evaluated as written, the a and b operands in mirror-image
+// positions.
+struct PxTerms {
+    float ln, ld, cn, cd;
+};
+
+__device__ __forceinline__ PxTerms px_terms(const float* m, float ca, float cb, const MetricTaps& t) {
 #pragma clang fp contract(off)
     const float ma = m[0], mb = m[1], e = t.sm1;
     const float ua = (ma + ca) + ca * e;                         // mu = mu' + S c
@@ -108,9 +115,30 @@ __device__ __forceinline__ float ssim_px(const float* m, float ca, float cb, con
     const float saa = (m[2] - ma * ma) - caa;
     const float sbb = (m[3] - mb * mb) - cbb;
     const float sab = (m[4] - ma * mb) - cab;
-    const float num = (2.f * (ua * ub) + t.c1) * (2.f * sab + t.c2);
-    const float den = ((ua * ua + ub * ub) + t.c1) * ((saa + sbb) + t.c2);
+    PxTerms p;
+    p.ln = 2.f * (ua * ub) + t.c1;
+    p.cn = 2.f * sab + t.c2;
+    p.ld = (ua * ua + ub * ub) + t.c1;
+    p.cd = (saa + sbb) + t.c2;
+    return p;
+}
+
+// SSIM of one pixel: (ln cn) / (ld cd)
+__device__ __forceinline__ float ssim_of(const PxTerms& p) {
+#pragma clang fp contract(off)
+    const float num = p.ln * p.cn;
+    const float den = p.ld * p.cd;
     return num / den;
+}
+
+// contrast-structure of one pixel (the multi-scale mode's cs): cn / cd, symmetric in (a, b) and 1 where they agree on the window
+__device__ __forceinline__ float cs_of(const PxTerms& p) {
+#pragma clang fp contract(off)
+    return p.cn / p.cd;
+}
+
+__device__ __forceinline__ float ssim_px(const float* m, float ca, float cb, const MetricTaps& t) {
+    return ssim_of(px_terms(m, ca, cb, t));
 }
 
 // one halo row's moments (h = a', b', a'^2, b'^2, a'b' about the row shifts) moved to the group centre: d = K_r - c
@@ -131,26 +159,15 @@ __device__ __forceinline__ double wave_sum(double v) {
     return v;
 }
 
+// The two passes of one tile, from the halos in sAB (sH: scratch of the horizontal pass): thread (tx = tid & 31, ty = tid >> 5)
+// gets the five moments of output pixels (4 ty + o, tx), o = 0 .. 3, about (cenA[o], cenB[o]).  The caller has synchronised
+// after writing sAB.
 template <int WIN>
-__global__ void __launch_bounds__(MTPB) image_metrics_tile_kernel(mmh_image_src A, mmh_image_src Bsrc, int C, int H, int W,
-                                                                  int tiles_x, MetricTaps taps, double* __restrict__ part) {
+__device__ __forceinline__ void tile_moments(const float2* sAB, float* sH, const MetricTaps& taps, int tid, float (&mom)[4][5],
+                                             float (&cenA)[4], float (&cenB)[4]) {
     constexpr int R = MT + WIN - 1;   // halo rows / columns
     constexpr int HALF = WIN / 2;
     constexpr int GV = WIN >= 5 ? 4 : 2;   // output rows per vertical group: every one within HALF rows of the centre
-    __shared__ float2 sAB[R * MROW];      // the two halos interleaved: one 8-byte LDS read per pixel pair
-    __shared__ __attribute__((aligned(16))) float sH[5 * R * HROW];
-    __shared__ double sRed[MTPB / 64][3];
-
-    const int tile = blockIdx.x, c = blockIdx.y, b = blockIdx.z;
-    const int y0 = (tile / tiles_x) * MT, x0 = (tile % tiles_x) * MT;
-    const int tid = threadIdx.x;
-    const int64_t baseA = (int64_t)b * A.sb + (int64_t)c * A.sc;
-    const int64_t baseB = (int64_t)b * Bsrc.sb + (int64_t)c * Bsrc.sc;
-
-    // halo -> LDS, mapped to [0, 1]; zero outside the image
-    load_halos<R>(A, baseA, Bsrc, baseB, y0 - HALF, x0 - HALF, H, W, sAB);
-    __syncthreads();
-
     // horizontal pass: row r, output columns 2 xg, 2 xg + 1, five moments of the values shifted by the halo pixel at the
     // centre of column 2 xg's row window (R * 16 items: 2.6 rounds of 256 threads at w = 11)
     for (int it = tid; it < R * (MT / 2); it += MTPB) {
@@ -192,7 +209,6 @@ __global__ void __launch_bounds__(MTPB) image_metrics_tile_kernel(mmh_image_src 
     // vertical pass: column tx, output rows 4 ty .. 4 ty + 3 in groups of GV rows about the pixel of the group's second row
     const int tx = tid & 31, ty = tid >> 5;
     const int kcol = (tx & ~1) + HALF;              // halo column of this column's horizontal shifts
-    float mom[4][5], cenA[4], cenB[4];
 #pragma unroll
     for (int g0 = 0; g0 < 4; g0 += GV) {
         const int row0 = ty * 4 + g0;                // halo row of the group's first window row
@@ -227,6 +243,30 @@ __global__ void __launch_bounds__(MTPB) image_metrics_tile_kernel(mmh_image_src 
             cenB[g0 + o] = cb;
         }
     }
+}
+
+template <int WIN>
+__global__ void __launch_bounds__(MTPB) image_metrics_tile_kernel(mmh_image_src A, mmh_image_src Bsrc, int C, int H, int W,
+                                                                  int tiles_x, MetricTaps taps, double* __restrict__ part) {
+    constexpr int R = MT + WIN - 1;   // halo rows / columns
+    constexpr int HALF = WIN / 2;
+    __shared__ float2 sAB[R * MROW];      // the two halos interleaved: one 8-byte LDS read per pixel pair
+    __shared__ __attribute__((aligned(16))) float sH[5 * R * HROW];
+    __shared__ double sRed[MTPB / 64][3];
+
+    const int tile = blockIdx.x, c = blockIdx.y, b = blockIdx.z;
+    const int y0 = (tile / tiles_x) * MT, x0 = (tile % tiles_x) * MT;
+    const int tid = threadIdx.x;
+    const int64_t baseA = (int64_t)b * A.sb + (int64_t)c * A.sc;
+    const int64_t baseB = (int64_t)b * Bsrc.sb + (int64_t)c * Bsrc.sc;
+
+    // halo -> LDS, mapped to [0, 1]; zero outside the image
+    load_halos<R>(A, baseA, Bsrc, baseB, y0 - HALF, x0 - HALF, H, W, sAB);
+    __syncthreads();
+
+    const int tx = tid & 31, ty = tid >> 5;
+    float mom[4][5], cenA[4], cenB[4];
+    tile_moments<WIN>(sAB, sH, taps, tid, mom, cenA, cenB);
     double s_ssim = 0.0, s_l1 = 0.0, s_se = 0.0;
     const int ox = x0 + tx;
 #pragma unroll
@@ -284,6 +324,216 @@ __global__ void __launch_bounds__(256) image_metrics_final_kernel(const double* 
     if (tid < 3) out[(int64_t)b * 3 + tid] = sRed[tid][0] * inv_count;
 }
 
+// ---- the two further modes: the same halos, passes and ssim_px; their workgroup reduction lies in sH, which the vertical pass
+// has finished with, so neither holds more LDS than the plain kernel
+
+// K sums of one workgroup in the plain kernel's order (lanes of a wave by wave_sum, then the four waves in order) -> p[0 .. K)
+template <int K>
+__device__ __forceinline__ void block_sums(double (&v)[K], double* sRed, int tid, double* p) {
+    __syncthreads();                   // every wave is through with sH
+#pragma unroll
+    for (int k = 0; k < K; ++k) v[k] = wave_sum(v[k]);
+    if ((tid & 63) == 0)
+#pragma unroll
+        for (int k = 0; k < K; ++k) sRed[(tid >> 6) * K + k] = v[k];
+    __syncthreads();
+    if (tid == 0) {
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            double t = sRed[k];
+#pragma unroll
+            for (int w = 1; w < MTPB / 64; ++w) t += sRed[w * K + k];
+            p[k] = t;
+        }
+    }
+}
+
+// Masked mode: per (tile, channel, image) seven partials - the plain kernel's three, the same three over the pixels whose mask
+// byte is non-zero (a pixel outside the mask adds 0.0 in its place, so an all-ones mask gives the plain sums' bits), and the
+// number of such pixels.
+template <int WIN>
+__global__ void __launch_bounds__(MTPB) image_metrics_masked_kernel(mmh_image_src A, mmh_image_src Bsrc, const uint8_t* __restrict__ mask,
+                                                                    int64_t msb, int64_t msh, int64_t msw, int C, int H, int W,
+                                                                    int tiles_x, MetricTaps taps, double* __restrict__ part) {
+    constexpr int R = MT + WIN - 1;
+    constexpr int HALF = WIN / 2;
+    __shared__ float2 sAB[R * MROW];
+    __shared__ __attribute__((aligned(16))) float sH[5 * R * HROW];
+
+    const int tile = blockIdx.x, c = blockIdx.y, b = blockIdx.z;
+    const int y0 = (tile / tiles_x) * MT, x0 = (tile % tiles_x) * MT;
+    const int tid = threadIdx.x;
+    const int tx = tid & 31, ty = tid >> 5;
+    const int ox = x0 + tx;
+    const int64_t baseA = (int64_t)b * A.sb + (int64_t)c * A.sc;
+    const int64_t baseB = (int64_t)b * Bsrc.sb + (int64_t)c * Bsrc.sc;
+
+    // this thread's four mask bytes, in flight under the halo load and the two passes
+    bool in[4];
+#pragma unroll
+    for (int o = 0; o < 4; ++o) {
+        const int oy = y0 + ty * 4 + o;
+        in[o] = oy < H && ox < W && mask[(int64_t)b * msb + (int64_t)oy * msh + (int64_t)ox * msw] != 0;
+    }
+    load_halos<R>(A, baseA, Bsrc, baseB, y0 - HALF, x0 - HALF, H, W, sAB);
+    __syncthreads();
+
+    float mom[4][5], cenA[4], cenB[4];
+    tile_moments<WIN>(sAB, sH, taps, tid, mom, cenA, cenB);
+    double s_ssim = 0.0, s_l1 = 0.0, s_se = 0.0, m_ssim = 0.0, m_l1 = 0.0, m_se = 0.0, m_n = 0.0;
+#pragma unroll
+    for (int o = 0; o < 4; ++o) {
+        const int oy = y0 + ty * 4 + o;
+        if (oy < H && ox < W) {
+            const double v = (double)ssim_px(mom[o], cenA[o], cenB[o], taps);
+            s_ssim += v;
+            const int li = (ty * 4 + o + HALF) * MROW + tx + HALF;
+            const double d = (double)sAB[li].x - (double)sAB[li].y;
+            s_l1 += fabs(d);
+            s_se += d * d;
+            const double dm = in[o] ? d : 0.0;      // a product of its own, so both sums are formed by the same instructions
+            m_ssim += in[o] ? v : 0.0;
+            m_l1 += fabs(dm);
+            m_se += dm * dm;
+            m_n += in[o] ? 1.0 : 0.0;
+        }
+    }
+    double v[7] = {s_ssim, s_l1, s_se, m_ssim, m_l1, m_se, m_n};
+    block_sums<7>(v, reinterpret_cast<double*>(sH), tid, part + (((int64_t)b * C + c) * (int64_t)gridDim.x + tile) * 7);
+}
+
+// one workgroup per image: the seven sums over its n partials in the plain final kernel's order.  The count partials of the C
+// channels add up to T = C * count exactly; the masked means are sum * (1.0 / T), NaN where the mask is empty.
+__global__ void __launch_bounds__(256) image_metrics_masked_final_kernel(const double* __restrict__ part, int n, int C,
+                                                                         double inv_count, double* __restrict__ out) {
+    __shared__ double sRed[7][256];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const double* p = part + (int64_t)b * n * 7;
+    double s[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int i = tid; i < n; i += 256)
+#pragma unroll
+        for (int k = 0; k < 7; ++k) s[k] += p[(int64_t)i * 7 + k];
+#pragma unroll
+    for (int k = 0; k < 7; ++k) sRed[k][tid] = s[k];
+    __syncthreads();
+    for (int h = 128; h > 0; h >>= 1) {
+        if (tid < h)
+#pragma unroll
+            for (int k = 0; k < 7; ++k) sRed[k][tid] += sRed[k][tid + h];
+        __syncthreads();
+    }
+    const double T = sRed[6][0];
+    if (tid < 3) out[(int64_t)b * 7 + tid] = sRed[tid][0] * inv_count;
+    else if (tid < 6) out[(int64_t)b * 7 + tid] = T > 0.0 ? sRed[tid][0] * (1.0 / T) : __builtin_nan("");
+    else if (tid == 6) out[(int64_t)b * 7 + 6] = T / (double)C;
+}
+
+// ((v00 + v01) + (v10 + v11)) * 0.25f as written
+__device__ __forceinline__ float pool4(float v00, float v01, float v10, float v11) {
+#pragma clang fp contract(off)
+    return ((v00 + v01) + (v10 + v11)) * 0.25f;
+}
+
+// Multi-scale mode, one level: per (tile, channel, image) two partials - the SSIM map and the contrast-structure map summed
+// over the output pixels whose whole window lies inside the image - and, when nextA is given, this tile's 16 x 16 part of the
+// next level's pair: pooled pixel (i, j) is the mean of rows 2 i - ph, 2 i - ph + 1 and columns 2 j - pw, 2 j - pw + 1 (ph = H % 2,
+// pw = W % 2; zero outside the image, divisor 4).  Row 2 i and column 2 j lie in this tile (its origin is even) and the row or
+// column before them in its halo, which is at least one pixel wide.
+template <int WIN>
+__global__ void __launch_bounds__(MTPB) ms_ssim_level_kernel(mmh_image_src A, mmh_image_src Bsrc, int C, int H, int W, int tiles_x,
+                                                             MetricTaps taps, double* __restrict__ part, float* __restrict__ nextA,
+                                                             float* __restrict__ nextB) {
+    constexpr int R = MT + WIN - 1;
+    constexpr int HALF = WIN / 2;
+    __shared__ float2 sAB[R * MROW];
+    __shared__ __attribute__((aligned(16))) float sH[5 * R * HROW];
+
+    const int tile = blockIdx.x, c = blockIdx.y, b = blockIdx.z;
+    const int y0 = (tile / tiles_x) * MT, x0 = (tile % tiles_x) * MT;
+    const int tid = threadIdx.x;
+    const int64_t baseA = (int64_t)b * A.sb + (int64_t)c * A.sc;
+    const int64_t baseB = (int64_t)b * Bsrc.sb + (int64_t)c * Bsrc.sc;
+
+    load_halos<R>(A, baseA, Bsrc, baseB, y0 - HALF, x0 - HALF, H, W, sAB);
+    __syncthreads();
+
+    if (nextA) {
+        const int Hn = (H + 1) >> 1, Wn = (W + 1) >> 1;
+        const int pi = tid >> 4, pj = tid & 15;
+        const int gi = (y0 >> 1) + pi, gj = (x0 >> 1) + pj;
+        if (gi < Hn && gj < Wn) {
+            const float2* q = sAB + (2 * pi - (H & 1) + HALF) * MROW + (2 * pj - (W & 1) + HALF);
+            const float2 v00 = q[0], v01 = q[1], v10 = q[MROW], v11 = q[MROW + 1];
+            const int64_t at = (((int64_t)b * C + c) * Hn + gi) * Wn + gj;
+            nextA[at] = pool4(v00.x, v01.x, v10.x, v11.x);
+            nextB[at] = pool4(v00.y, v01.y, v10.y, v11.y);
+        }
+    }
+
+    const int tx = tid & 31, ty = tid >> 5;
+    float mom[4][5], cenA[4], cenB[4];
+    tile_moments<WIN>(sAB, sH, taps, tid, mom, cenA, cenB);
+    double s_ssim = 0.0, s_cs = 0.0;
+    const int ox = x0 + tx;
+#pragma unroll
+    for (int o = 0; o < 4; ++o) {
+        const int oy = y0 + ty * 4 + o;
+        if (oy >= HALF && oy < H - HALF && ox >= HALF && ox < W - HALF) {
+            const PxTerms p = px_terms(mom[o], cenA[o], cenB[o], taps);
+            s_ssim += (double)ssim_of(p);
+            s_cs += (double)cs_of(p);
+        }
+    }
+    double v[2] = {s_ssim, s_cs};
+    block_sums<2>(v, reinterpret_cast<double*>(sH), tid, part + (((int64_t)b * C + c) * (int64_t)gridDim.x + tile) * 2);
+}
+
+constexpr int MS_MAX_LEVELS = 5;
+
+struct MsPlan {
+    int levels;
+    int H[MS_MAX_LEVELS], W[MS_MAX_LEVELS], tiles[MS_MAX_LEVELS];
+    int64_t part_at[MS_MAX_LEVELS];        // doubles from the workspace's start: level l's [B][C][tiles][2]
+    int64_t pyr_at[MS_MAX_LEVELS];         // bytes from the workspace's start: level l's a then b, fp32 [B][C][H_l][W_l] each (l >= 1)
+    double inv_count[MS_MAX_LEVELS];       // 1.0 / ((H_l - w + 1)(W_l - w + 1))
+    double weight[MS_MAX_LEVELS];
+    int64_t bytes;
+};
+
+// one workgroup per image: per channel and level the partials of that level in a fixed order (strided per thread, then a fixed
+// tree) times 1 / count -> scales; cs for every level but the last, SSIM for the last; out = (sum over c of the product over l of
+// pow(max(v, 0), weight)) / C
+__global__ void __launch_bounds__(256) ms_ssim_final_kernel(const double* __restrict__ ws, int C, MsPlan plan,
+                                                            double* __restrict__ scales, double* __restrict__ out) {
+    __shared__ double sRed[256];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    double total = 0.0;
+    for (int c = 0; c < C; ++c) {
+        double prod = 1.0;
+#pragma unroll
+        for (int l = 0; l < MS_MAX_LEVELS; ++l) {
+            if (l < plan.levels) {
+                const int n = plan.tiles[l];
+                const double* p = ws + plan.part_at[l] + ((int64_t)b * C + c) * n * 2 + (l == plan.levels - 1 ? 0 : 1);
+                double s = 0.0;
+                for (int i = tid; i < n; i += 256) s += p[(int64_t)i * 2];
+                sRed[tid] = s;
+                __syncthreads();
+                for (int h = 128; h > 0; h >>= 1) {
+                    if (tid < h) sRed[tid] += sRed[tid + h];
+                    __syncthreads();
+                }
+                const double v = sRed[0] * plan.inv_count[l];
+                __syncthreads();               // sRed[0] is read before the next level overwrites it
+                if (tid == 0) scales[((int64_t)b * C + c) * plan.levels + l] = v;
+                prod *= pow(fmax(v, 0.0), plan.weight[l]);
+            }
+        }
+        total += prod;
+    }
+    if (tid == 0) out[b] = total / (double)C;
+}
+
 int64_t metric_tiles(int H, int W) { return mmh::cdiv(H, MT) * mmh::cdiv(W, MT); }
 
 bool metric_shape_ok(int B, int C, int H, int W, int window) {
@@ -293,41 +543,41 @@ bool metric_shape_ok(int B, int C, int H, int W, int window) {
            metric_tiles(H, W) * MTPB < (int64_t(1) << 32) && (int64_t)C * metric_tiles(H, W) < (int64_t(1) << 31);
 }
 
-template <int WIN>
-void launch_tiles(const mmh_image_src& a, const mmh_image_src& b, int B, int C, int H, int W, const MetricTaps& t,
-                  double* part, hipStream_t s) {
-    const int tiles_x = (int)mmh::cdiv(W, MT);
-    hipLaunchKernelGGL(image_metrics_tile_kernel<WIN>, dim3((unsigned)metric_tiles(H, W), C, B), dim3(MTPB), 0, s, a, b, C, H, W,
-                       tiles_x, t, part);
+// f(std::integral_constant<int, window>) for the odd windows 3 .. 15 (the caller has checked the range)
+template <typename F>
+void with_window(int window, F&& f) {
+    switch (window) {
+        case 3: f(std::integral_constant<int, 3>{}); break;
+        case 5: f(std::integral_constant<int, 5>{}); break;
+        case 7: f(std::integral_constant<int, 7>{}); break;
+        case 9: f(std::integral_constant<int, 9>{}); break;
+        case 11: f(std::integral_constant<int, 11>{}); break;
+        case 13: f(std::integral_constant<int, 13>{}); break;
+        default: f(std::integral_constant<int, 15>{}); break;
+    }
 }
 
-}  // namespace
-
-size_t mmh_image_metrics_ws_bytes(int B, int C, int H, int W, int window) {
-    if (!metric_shape_ok(B, C, H, W, window)) return 0;
-    return (size_t)B * C * metric_tiles(H, W) * 3 * sizeof(double);
-}
-
-int mmh_image_metrics(const mmh_image_src* a, const mmh_image_src* b, int B, int C, int H, int W, int window, const float* taps,
-                      double c1, double c2, void* ws, size_t ws_bytes, double* out, mmh_stream_t s) {
-    MMH_REQUIRE(a && b && a->ptr && b->ptr && ws && out, "mmh_image_metrics: NULL argument");
-    MMH_REQUIRE(window >= 3 && window <= 15 && window % 2 == 1, "mmh_image_metrics: window %d (odd, 3 .. 15)", window);
-    MMH_REQUIRE(metric_shape_ok(B, C, H, W, window), "mmh_image_metrics: bad shape B=%d C=%d H=%d W=%d", B, C, H, W);
-    MMH_REQUIRE(taps && c1 > 0 && c2 > 0, "mmh_image_metrics: taps must be given, c1 and c2 > 0");
+// the argument checks the three entry points share (fn: the entry point's name in the message)
+int check_pair(const char* fn, const mmh_image_src* a, const mmh_image_src* b, int B, int C, int H, int W, int window,
+               const float* taps, double c1, double c2, const void* ws, const void* out) {
+    MMH_REQUIRE(a && b && a->ptr && b->ptr && ws && out, "%s: NULL argument", fn);
+    MMH_REQUIRE(window >= 3 && window <= 15 && window % 2 == 1, "%s: window %d (odd, 3 .. 15)", fn, window);
+    MMH_REQUIRE(metric_shape_ok(B, C, H, W, window), "%s: bad shape B=%d C=%d H=%d W=%d", fn, B, C, H, W);
+    MMH_REQUIRE(taps && c1 > 0 && c2 > 0, "%s: taps must be given, c1 and c2 > 0", fn);
     double tsum = 0.0;
     for (int i = 0; i < window; ++i) {
-        MMH_REQUIRE(taps[i] > 0.f && taps[i] < 1.f, "mmh_image_metrics: tap %d = %g (a normalised window has taps in (0, 1))", i,
-                    (double)taps[i]);
+        MMH_REQUIRE(taps[i] > 0.f && taps[i] < 1.f, "%s: tap %d = %g (a normalised window has taps in (0, 1))", fn, i, (double)taps[i]);
         tsum += taps[i];
     }
-    MMH_REQUIRE(std::fabs(tsum - 1.0) < 1e-5, "mmh_image_metrics: the taps sum to %.9g, not 1", tsum);
+    MMH_REQUIRE(std::fabs(tsum - 1.0) < 1e-5, "%s: the taps sum to %.9g, not 1", fn, tsum);
     for (const mmh_image_src* p : {a, b})
-        MMH_REQUIRE(p->dtype == MMH_F32 || p->dtype == MMH_BF16 || p->dtype == MMH_FP16 || p->dtype == MMH_U8,
-                    "mmh_image_metrics: unknown dtype %d", p->dtype);
-    const size_t need = mmh_image_metrics_ws_bytes(B, C, H, W, window);
-    MMH_REQUIRE(need > 0 && ws_bytes >= need, "mmh_image_metrics: workspace %zu bytes < %zu", ws_bytes, need);
+        MMH_REQUIRE(p->dtype == MMH_F32 || p->dtype == MMH_BF16 || p->dtype == MMH_FP16 || p->dtype == MMH_U8, "%s: unknown dtype %d", fn,
+                    p->dtype);
+    return 0;
+}
 
-    // the 2-D window is the fp32 outer product of the taps (pytorch_ssim.create_window); its sum, in float64, gives S - 1
+// the 2-D window is the fp32 outer product of the taps (pytorch_ssim.create_window); its sum, in float64, gives S - 1
+MetricTaps metric_taps(int window, const float* taps, double c1, double c2) {
     MetricTaps t{};
     float tsum32 = 0.f;
     for (int i = 0; i < window; ++i) {
@@ -342,20 +592,134 @@ int mmh_image_metrics(const mmh_image_src* a, const mmh_image_src* b, int B, int
     t.sm1 = (float)(s2 - 1.0);
     t.c1 = (float)c1;
     t.c2 = (float)c2;
+    return t;
+}
 
+// the multi-scale mode's levels, partial and pyramid offsets; false = the arguments are refused
+bool ms_plan(int B, int C, int H, int W, int window, int levels, MsPlan& p) {
+    if (!metric_shape_ok(B, C, H, W, window) || levels < 1 || levels > MS_MAX_LEVELS) return false;
+    if ((int64_t)std::min(H, W) <= ((int64_t)(window - 1) << (levels - 1))) return false;      // the last level holds a window
+    if ((double)B * C * H * W > 1e12) return false;                                            // the pyramid's byte count
+    p = MsPlan{};
+    p.levels = levels;
+    int64_t doubles = 0;
+    for (int l = 0; l < levels; ++l) {
+        p.H[l] = H;
+        p.W[l] = W;
+        p.tiles[l] = (int)metric_tiles(H, W);
+        p.part_at[l] = doubles;
+        doubles += (int64_t)B * C * p.tiles[l] * 2;
+        p.inv_count[l] = 1.0 / ((double)(H - window + 1) * (double)(W - window + 1));
+        H = (H + 1) / 2;
+        W = (W + 1) / 2;
+    }
+    int64_t bytes = doubles * (int64_t)sizeof(double);
+    for (int l = 1; l < levels; ++l) {
+        p.pyr_at[l] = bytes;
+        bytes += 2 * (int64_t)B * C * p.H[l] * p.W[l] * (int64_t)sizeof(float);
+    }
+    p.bytes = bytes;
+    return true;
+}
+
+}  // namespace
+
+size_t mmh_image_metrics_ws_bytes(int B, int C, int H, int W, int window) {
+    if (!metric_shape_ok(B, C, H, W, window)) return 0;
+    return (size_t)B * C * metric_tiles(H, W) * 3 * sizeof(double);
+}
+
+int mmh_image_metrics(const mmh_image_src* a, const mmh_image_src* b, int B, int C, int H, int W, int window, const float* taps,
+                      double c1, double c2, void* ws, size_t ws_bytes, double* out, mmh_stream_t s) {
+    if (int rc = check_pair("mmh_image_metrics", a, b, B, C, H, W, window, taps, c1, c2, ws, out)) return rc;
+    const size_t need = mmh_image_metrics_ws_bytes(B, C, H, W, window);
+    MMH_REQUIRE(need > 0 && ws_bytes >= need, "mmh_image_metrics: workspace %zu bytes < %zu", ws_bytes, need);
+    const MetricTaps t = metric_taps(window, taps, c1, c2);
     hipStream_t st = mmh::as_stream(s);
     double* part = static_cast<double*>(ws);
-    switch (window) {
-        case 3: launch_tiles<3>(*a, *b, B, C, H, W, t, part, st); break;
-        case 5: launch_tiles<5>(*a, *b, B, C, H, W, t, part, st); break;
-        case 7: launch_tiles<7>(*a, *b, B, C, H, W, t, part, st); break;
-        case 9: launch_tiles<9>(*a, *b, B, C, H, W, t, part, st); break;
-        case 11: launch_tiles<11>(*a, *b, B, C, H, W, t, part, st); break;
-        case 13: launch_tiles<13>(*a, *b, B, C, H, W, t, part, st); break;
-        default: launch_tiles<15>(*a, *b, B, C, H, W, t, part, st); break;
-    }
+    const int tiles_x = (int)mmh::cdiv(W, MT);
+    with_window(window, [&](auto w) {
+        hipLaunchKernelGGL(image_metrics_tile_kernel<decltype(w)::value>, dim3((unsigned)metric_tiles(H, W), C, B), dim3(MTPB), 0, st,
+                           *a, *b, C, H, W, tiles_x, t, part);
+    });
     if (int rc = mmh::check_launch("image_metrics_tile")) return rc;
     const int n = (int)(C * metric_tiles(H, W));
     hipLaunchKernelGGL(image_metrics_final_kernel, dim3(B), dim3(256), 0, st, part, n, 1.0 / ((double)C * H * W), out);
     return mmh::check_launch("image_metrics_final");
 }
+
+size_t mmh_image_metrics_masked_ws_bytes(int B, int C, int H, int W, int window) {
+    if (!metric_shape_ok(B, C, H, W, window)) return 0;
+    return (size_t)B * C * metric_tiles(H, W) * 7 * sizeof(double);
+}
+
+int mmh_image_metrics_masked(const mmh_image_src* a, const mmh_image_src* b, const uint8_t* mask, int64_t msb, int64_t msh,
+                             int64_t msw, int B, int C, int H, int W, int window, const float* taps, double c1, double c2, void* ws,
+                             size_t ws_bytes, double* out, mmh_stream_t s) {
+    if (int rc = check_pair("mmh_image_metrics_masked", a, b, B, C, H, W, window, taps, c1, c2, ws, out)) return rc;
+    MMH_REQUIRE(mask, "mmh_image_metrics_masked: NULL mask");
+    const size_t need = mmh_image_metrics_masked_ws_bytes(B, C, H, W, window);
+    MMH_REQUIRE(need > 0 && ws_bytes >= need, "mmh_image_metrics_masked: workspace %zu bytes < %zu", ws_bytes, need);
+    const MetricTaps t = metric_taps(window, taps, c1, c2);
+    hipStream_t st = mmh::as_stream(s);
+    double* part = static_cast<double*>(ws);
+    const int tiles_x = (int)mmh::cdiv(W, MT);
+    with_window(window, [&](auto w) {
+        hipLaunchKernelGGL(image_metrics_masked_kernel<decltype(w)::value>, dim3((unsigned)metric_tiles(H, W), C, B), dim3(MTPB), 0,
+                           st, *a, *b, mask, msb, msh, msw, C, H, W, tiles_x, t, part);
+    });
+    if (int rc = mmh::check_launch("image_metrics_masked")) return rc;
+    const int n = (int)(C * metric_tiles(H, W));
+    hipLaunchKernelGGL(image_metrics_masked_final_kernel, dim3(B), dim3(256), 0, st, part, n, C, 1.0 / ((double)C * H * W), out);
+    return mmh::check_launch("image_metrics_masked_final");
+}
+
+size_t mmh_ms_ssim_ws_bytes(int B, int C, int H, int W, int window, int levels) {
+    MsPlan p;
+    return ms_plan(B, C, H, W, window, levels, p) ? (size_t)p.bytes : 0;
+}
+
+int mmh_ms_ssim(const mmh_image_src* a, const mmh_image_src* b, int B, int C, int H, int W, int window, const float* taps, double c1,
+                double c2, int levels, const double* weights, void* ws, size_t ws_bytes, double* scales, double* out,
+                mmh_stream_t s) {
+    if (int rc = check_pair("mmh_ms_ssim", a, b, B, C, H, W, window, taps, c1, c2, ws, out)) return rc;
+    MMH_REQUIRE(scales && weights, "mmh_ms_ssim: NULL argument");
+    MMH_REQUIRE(levels >= 1 && levels <= MS_MAX_LEVELS, "mmh_ms_ssim: levels %d (1 .. %d)", levels, MS_MAX_LEVELS);
+    MsPlan plan;
+    MMH_REQUIRE(ms_plan(B, C, H, W, window, levels, plan),
+                "mmh_ms_ssim: bad shape H=%d W=%d: min(H, W) must exceed (window - 1) * 2^(levels - 1) = %d", H, W,
+                (window - 1) << (levels - 1));
+    for (int l = 0; l < levels; ++l) {
+        MMH_REQUIRE(weights[l] > 0.0 && std::isfinite(weights[l]), "mmh_ms_ssim: weight %d = %g (finite, > 0)", l, weights[l]);
+        plan.weight[l] = weights[l];
+    }
+    MMH_REQUIRE(ws_bytes >= (size_t)plan.bytes, "mmh_ms_ssim: workspace %zu bytes < %zu", ws_bytes, (size_t)plan.bytes);
+    MMH_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 7) == 0, "mmh_ms_ssim: the workspace must be 8-byte aligned");
+    const MetricTaps t = metric_taps(window, taps, c1, c2);
+    hipStream_t st = mmh::as_stream(s);
+    double* part = static_cast<double*>(ws);
+    mmh_image_src la = *a, lb = *b;
+    for (int l = 0; l < levels; ++l) {
+        const int Hl = plan.H[l], Wl = plan.W[l];
+        float *na = nullptr, *nb = nullptr;
+        int64_t plane = 0;
+        if (l + 1 < levels) {       // the next level's pair, written by this level's launch
+            plane = (int64_t)plan.H[l + 1] * plan.W[l + 1];
+            na = reinterpret_cast<float*>(static_cast<char*>(ws) + plan.pyr_at[l + 1]);
+            nb = na + (int64_t)B * C * plane;
+        }
+        const int tiles_x = (int)mmh::cdiv(Wl, MT);
+        with_window(window, [&](auto w) {
+            hipLaunchKernelGGL(ms_ssim_level_kernel<decltype(w)::value>, dim3((unsigned)plan.tiles[l], C, B), dim3(MTPB), 0, st, la, lb,
+                               C, Hl, Wl, tiles_x, t, part + plan.part_at[l], na, nb);
+        });
+        if (int rc = mmh::check_launch("ms_ssim_level")) return rc;
+        if (na) {
+            la = mmh_image_src{na, MMH_F32, 1.f, 0.f, C * plane, plane, plan.W[l + 1], 1};
+            lb = mmh_image_src{nb, MMH_F32, 1.f, 0.f, C * plane, plane, plan.W[l + 1], 1};
+        }
+    }
+    hipLaunchKernelGGL(ms_ssim_final_kernel, dim3(B), dim3(256), 0, st, part, C, plan, scales, out);
+    return mmh::check_launch("ms_ssim_final");
+}
+

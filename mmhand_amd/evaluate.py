@@ -7,7 +7,7 @@ scores each output against its target image H2:
     python -m mmhand_amd.evaluate --name CKP [--checkpoints_dir checkpoints] [--which_epoch latest] --dataroot DIR
         --dataset rhd|stb [--augmentation_ratio R] [--batchSize 16] [--bf16] [--gpu 0] [--window 11]
         [--resize_inputs N] [--pairing P [--match_pool M]] [--depth_source files|joints [--render_radius R] [--render_bg Z]]
-        [--results_json PATH] [--per_image_csv PATH]
+        [--ms_ssim] [--hand_region [--hand_radius R]] [--results_json PATH] [--per_image_csv PATH]
 
 Directory mode - scores the PNGs aug.py wrote (<DIR>/<folder of the target>/<name>) against the target colour PNGs:
 
@@ -80,7 +80,27 @@ Two-directory mode - two directories of PNGs paired by relative file name, no la
 
     python -m mmhand_amd.evaluate --lpips_images DIR --lpips_ref DIR --lpips <pth> --lpips_lin <pth>|uniform [--batchSize 16] ...
 
-No VGG-16 or LPIPS weights ship with this repository or the reference: a distance means what its files mean."""
+No VGG-16 or LPIPS weights ship with this repository or the reference: a distance means what its files mean.
+
+`--ms_ssim`: also multi-scale SSIM (Wang, Simoncelli, Bovik 2003; mmhand_amd/metrics.py ms_ssim, mmh_ms_ssim) of the pair SSIM
+scores, with --window: five scales with the paper's weights, the contrast-structure term of the first four and the SSIM of the
+last, each over the pixels whose window lies inside the image, 2 x 2 average pooling in between - `MS_SSIM_avg`, `MS_SSIM_std`
+and `ms_weights` in the summary, an `ms_ssim` column in the per-image CSV.  The image's smaller side must exceed
+(window - 1) * 16 (160 at the default window); a smaller image ends the run before anything is scored (see --resize_inputs).
+
+`--hand_region [--hand_radius R]`: also SSIM, L1 and PSNR over the hand alone.  About a quarter of a frame lies under a bone;
+the rest is background the generator mostly carries over, and it dominates the whole-image figures.  The region is the coverage
+of the TARGET pose's 20 bones drawn as capsules of R pixels of the scored grid (ops.render_pose_depth on the labels' joints, at
+the files' size or on the --resize_inputs grid); R defaults to 10 * H / 256, a definition and not a tuned value - capsules of
+that radius leave gaps in the palm between the metacarpals, a larger R closes them.  The same SSIM map, |a-b| and (a-b)^2 as the
+whole-image figures, averaged over the region, from the same pass (mmh_image_metrics_masked) - `SSIM_hand_avg`, `SSIM_hand_std`,
+`L1_hand_avg`, `PSNR_hand_avg`, `hand_fraction_avg` (region pixels / (H W)), all over the `n_hand` images whose region is not
+empty, and `hand_radius` in the summary; `ssim_hand`, `l1_hand`, `psnr_hand`, `hand_fraction` columns in the per-image CSV.  The
+name is "hand", not "mask-SSIM", on purpose: PATN's mask-SSIM multiplies both images by the mask before scoring the whole
+frame, which this does not.
+
+Both flags apply to generator and directory mode alike.  Without them nothing of this is launched and both files are what they
+were."""
 import argparse
 import csv
 import json
@@ -152,6 +172,15 @@ def build_parser():
     p.add_argument("--lpips_lin", default=None, help="with --lpips: the lpips package's linear heads (lin{0..4}.model.1.weight), "
                                                      "or 'uniform' for the unweighted form; required with --lpips")
     p.add_argument("--lpips_ref", default=None, help="with --lpips_images: the directory of the reference PNGs, same relative names")
+    p.add_argument("--ms_ssim", action="store_true",
+                   help="also multi-scale SSIM (5 scales, the weights of Wang, Simoncelli, Bovik 2003) of the pair SSIM scores, with "
+                        "--window; the image's smaller side must exceed (window - 1) * 16 (160 at the default window)")
+    p.add_argument("--hand_region", action="store_true",
+                   help="also SSIM, L1 and PSNR over the hand alone: the pixels under one of the target pose's 20 bones, drawn as "
+                        "capsules of --hand_radius pixels from the target's labels")
+    p.add_argument("--hand_radius", type=float, default=None,
+                   help="with --hand_region: half-width of a bone in pixels of the scored grid; default 10 * H / 256.  Capsules of "
+                        "the default radius leave gaps in the palm between the metacarpals; a larger radius closes them")
     return p
 
 
@@ -408,6 +437,49 @@ def _pose_labels(loader, paths, size=None):
     return np.stack(uv), np.stack(depth)
 
 
+REGION_FLAGS = ("ms_ssim", "hand_region", "hand_radius")
+MS_LEVELS = 5
+
+
+def _meter(args, rng):
+    """the SSIM / L1 / PSNR meter; --ms_ssim and --hand_region add their columns to it, and without them it is the plain one"""
+    return QualityMeter(rng, args.window, ms_ssim=args.ms_ssim, hand=args.hand_region)
+
+
+def _scored_size(loader):
+    """(H, W) of the scored grid: --resize_inputs N, or the first target file's size"""
+    from .data import png_size
+    if loader.out_size:
+        return loader.out_size, loader.out_size
+    return png_size(loader.image_target[0]) if len(loader.image_target) else None
+
+
+def _check_ms_size(args, loader):
+    """--ms_ssim: the min-side rule of mmh_ms_ssim, before anything is scored"""
+    from .metrics import ms_ssim_min_side
+    size = _scored_size(loader) if args.ms_ssim else None
+    if size is not None and min(size) <= ms_ssim_min_side(args.window, MS_LEVELS):
+        raise SystemExit(f"evaluate: --ms_ssim: images of {size[0]} x {size[1]}: the smaller side must exceed (window - 1) * "
+                         f"2^(levels - 1) = {ms_ssim_min_side(args.window, MS_LEVELS)} for {MS_LEVELS} levels at --window "
+                         f"{args.window} (see --resize_inputs)")
+
+
+def hand_radius(args, H):
+    """--hand_radius, or its default on an H-row grid: 10 pixels at 256 rows, in proportion"""
+    return float(args.hand_radius) if args.hand_radius is not None else 10.0 * H / 256.0
+
+
+def _hand_masks(args, loader, meter, targets, H, W, dev):
+    """--hand_region: the targets' hand masks uint8 [B,H,W] on the scored grid, from their labels (the radius used is left on
+    the meter for the summary); None without the flag"""
+    if not args.hand_region:
+        return None
+    from .metrics import hand_mask
+    uv, _ = _pose_labels(loader, targets, loader.out_size)
+    meter.hand_radius = hand_radius(args, H)
+    return hand_mask(torch.from_numpy(uv).to(dev), (H, W), meter.hand_radius)
+
+
 def _score_generator(args, ckpt, dev):
     from .data import HandFolderLoader
     from .inference import InferenceGenerator
@@ -420,12 +492,13 @@ def _score_generator(args, ckpt, dev):
     net.load_state_dict(sd)
     gen = InferenceGenerator(net.to(dev).eval(), use_graph=True, bf16=args.bf16)
     loader = HandFolderLoader(_opt(args), device=dev, decoded=True)
-    meter = QualityMeter("pm1", args.window)
+    _check_ms_size(args, loader)
+    meter = _meter(args, "pm1")
     for s in loader:
         fake = gen([s["H1"], torch.cat((s["P1"], s["P2"]), 1), torch.cat((s["D1"], s["D2"]), 1)])
         # gen returns its graph's static output buffer: the metric is enqueued here, before the next replay
         paths = [{"target": t, "source": h} for t, h in zip(s["H2_path"], s["H1_path"])]
-        meter.feed(fake, s["H2"], paths)
+        meter.feed(fake, s["H2"], paths, _hand_masks(args, loader, meter, s["H2_path"], fake.shape[2], fake.shape[3], dev))
         if est is not None:     # the fake batch as it lies on the device: min-max normalised by the estimator's first kernel
             est.feed(fake, *_pose_labels(loader, s["H2_path"], loader.out_size), paths=paths)
         if fsc is not None:     # FID / KID: the fake batch against its targets; --inception may ride on the same forward
@@ -463,7 +536,8 @@ def _score_directory(args, dev):
     size = loader.out_size
     # at the files' size both sides are bytes; at --resize_inputs N the targets are the decode pass's fp32 images, and the
     # PNGs' bytes are mapped to the same [-1, 1] range
-    meter = QualityMeter("pm1" if size else "u8_bgr_hwc", args.window)
+    _check_ms_size(args, loader)
+    meter = _meter(args, "pm1" if size else "u8_bgr_hwc")
     est, isc = _estimator(args, dev), _scorer(args, dev)
     fsc, lsc = _fid_scorer(args, dev, isc), _lpips_scorer(args, dev)
     idx = loader.indices()
@@ -477,6 +551,7 @@ def _score_directory(args, dev):
             if g.shape != want:
                 raise SystemExit(f"--generated: {t}: generated image {g.shape} vs target {want}")
         g8 = torch.from_numpy(np.stack(gen)).to(dev)
+        mask = _hand_masks(args, loader, meter, tgts, g8.shape[1], g8.shape[2], dev)
         if est is not None:     # the PNGs' bytes, B,G,R as they were read
             est.feed(g8, *_pose_labels(loader, tgts, size), paths=[{"target": t, "source": s} for t, s in zip(tgts, srcs)],
                      layout="bgr_hwc")
@@ -496,10 +571,10 @@ def _score_directory(args, dev):
         if size:
             pred = (g8.flip(-1).permute(0, 3, 1, 2).float() / 255.0 - 0.5) / 0.5
             meter.feed(pred, _targets_at(torch.from_numpy(np.stack(ref)).to(dev).contiguous(), size),
-                       [{"target": t, "source": s} for t, s in zip(tgts, srcs)])
+                       [{"target": t, "source": s} for t, s in zip(tgts, srcs)], mask)
             continue
         meter.feed(g8, torch.from_numpy(np.stack(ref)).to(dev),
-                   [{"target": t, "source": s} for t, s in zip(tgts, srcs)])
+                   [{"target": t, "source": s} for t, s in zip(tgts, srcs)], mask)
     return meter, {}, _pose_distances(args, loader), est, isc, fsc, lsc
 
 
@@ -660,6 +735,15 @@ def main(argv=None):
         parser.error("--lpips_ref belongs to --lpips_images")
     if args.lpips and (args.is_images or args.pck_images or args.fid_images):
         parser.error("--lpips scores image pairs: not with --is_images / --pck_images / --fid_images (see --lpips_images)")
+    if args.hand_radius is not None and not args.hand_region:
+        parser.error("--hand_radius belongs to --hand_region")
+    if args.hand_radius is not None and not (args.hand_radius >= 0 and np.isfinite(args.hand_radius)):
+        parser.error("--hand_radius must be finite and >= 0")
+    if (args.ms_ssim or args.hand_region) and not (args.name or args.generated):
+        parser.error("--ms_ssim / --hand_region score image pairs against their targets: with --name or --generated only")
+    if not (args.name or args.generated):       # the other modes' option dumps never knew these flags
+        for k in REGION_FLAGS:
+            delattr(args, k)
     if args.is_images:
         return _main_is_images(args)
     if args.fid_images:
@@ -684,6 +768,10 @@ def main(argv=None):
     meter, config, pose_d, est, isc, fsc, lsc = _score_generator(args, ckpt, dev) if ckpt else _score_directory(args, dev)
     res = meter.result()
     summary = res["summary"]
+    if args.hand_region:
+        summary["hand_radius"] = getattr(meter, "hand_radius", None)
+    meter_cols = ((["ms_ssim"] if args.ms_ssim else []) +
+                  (["ssim_hand", "l1_hand", "psnr_hand", "hand_fraction"] if args.hand_region else []))
     pck_cols = _pck_summary(args, est, summary, res["rows"])[1] if est is not None else []
     if isc is not None:
         _is_summary(isc, summary, res["rows"])
@@ -716,12 +804,16 @@ def main(argv=None):
             options = {k: v for k, v in options.items() if k not in FID_FLAGS}
         if lsc is None:                         # and LPIPS's: only under --lpips
             options = {k: v for k, v in options.items() if k not in LPIPS_FLAGS}
+        if not args.ms_ssim:                    # and the multi-scale and hand-region flags, each only when given
+            options = {k: v for k, v in options.items() if k != "ms_ssim"}
+        if not args.hand_region:
+            options = {k: v for k, v in options.items() if k not in ("hand_region", "hand_radius")}
         json.dump({"summary": summary, "options": options, "generator": config or None,
                    "domain": "[0, 1]: generator output (x + 1) / 2, PNG pixels u8 / 255"}, fh, indent=1)
     if args.per_image_csv:
         with open(args.per_image_csv, "w", newline="") as fh:
             w = csv.writer(fh)
-            extra = (["pose_distance"] if pose_d is not None else []) + pck_cols
+            extra = meter_cols + (["pose_distance"] if pose_d is not None else []) + pck_cols
             w.writerow(["target", "source", "ssim", "l1", "psnr"] + extra)
             for r in res["rows"]:
                 w.writerow([r["target"], r["source"], repr(r["ssim"]), repr(r["l1"]), repr(r["psnr"])] + [repr(r[k]) for k in extra])

@@ -211,6 +211,11 @@ SIGNATURES = {
     "mmh_allreduce_bucket": (_i, [_vp, _vp, _i64, _i, _vp]),
     "mmh_image_metrics_ws_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "mmh_image_metrics": (_i, [C.POINTER(ImageSrc), C.POINTER(ImageSrc), _i, _i, _i, _i, _i, _vp, _d, _d, _vp, _sz, _vp, _vp]),
+    "mmh_image_metrics_masked_ws_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "mmh_image_metrics_masked": (_i, [C.POINTER(ImageSrc), C.POINTER(ImageSrc), _vp, _i64, _i64, _i64, _i, _i, _i, _i, _i, _vp, _d, _d,
+                                      _vp, _sz, _vp, _vp]),
+    "mmh_ms_ssim_ws_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
+    "mmh_ms_ssim": (_i, [C.POINTER(ImageSrc), C.POINTER(ImageSrc), _i, _i, _i, _i, _i, _vp, _d, _d, _i, _vp, _vp, _sz, _vp, _vp, _vp]),
     "mmh_png_decode_batch": (_i, [_vp, _i64, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _vp]),
     "mmh_png_encode_slot_bytes": (_i64, [_i, _i]),
     "mmh_png_encode_scratch_bytes": (_i64, [_i, _i, _i]),
